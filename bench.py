@@ -16,7 +16,14 @@ N>1 (torch.distributed.run, one rank per GPU): the 64 frames are sharded
 stays 131,072 rays per step (strong scaling) and value =
 131,072 rays / max-over-ranks step time.
 
-At N=1 the same JSON line also carries the other BASELINE configurations,
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+exactly K steps (default: one training round of n_step + 1 = 501), writes the last
+step's outputs when --dump-outputs DIR is given, and prints the result line.
+Everything else is behind --full: the other execution mode, the per-kernel /
+roofline / MFMA pass, the ray-pool timing, the side configurations and the CPU
+baselines.
+
+With --full at N=1 the same JSON line also carries the other BASELINE configurations,
 each on a fresh scene and fresh models with the same protocol: `config2`
 (16-frame pool, 32,768 rays/step), `parity_mode` (NerfRunner.train()'s
 N_rand=2048 rays per step drawn by the epoch randperm over the 64-frame pool)
@@ -153,7 +160,7 @@ def rank_frames(rank, world, frames_per_gpu, cfg_over):
     return cfg, seq_local, poses_n, pts, lo, hi
 
 
-def build_rank_scene(rank, world, frames_per_gpu, cfg_over, dev):
+def build_rank_scene(rank, world, frames_per_gpu, cfg_over, dev, time_pool=False):
     from bundlesdf_amd import synthetic as SY
     from bundlesdf_amd.octree import build_occupancy, coarsen
     from bundlesdf_amd.ray_pool import PointGrid, make_pool_rays
@@ -171,15 +178,17 @@ def build_rank_scene(rank, world, frames_per_gpu, cfg_over, dev):
     grid = PointGrid(pts, 0.02 * sc, dev)
     pool_kw = dict(occ=occ, point_grid=grid, device=dev, index_base=lo)
     pool = make_pool_rays(*pool_args, **pool_kw)
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(3):
-        pool = make_pool_rays(*pool_args, **pool_kw)
-    torch.cuda.synchronize(dev)
-    pool_ms = (time.perf_counter() - t0) / 3 * 1e3
-    pool_info = {"frames": hi - lo, "pixels": int((hi - lo) * SY.H_IMG * SY.W_IMG), "rays": int(len(pool)),
-                 "ms": round(pool_ms, 2), "Mpixel_per_s": round((hi - lo) * SY.H_IMG * SY.W_IMG / pool_ms / 1e3, 1),
-                 "includes": "H2D upload of the frames + 5 HIP launches + n_out readback (make_pool_rays)"}
+    pool_info = {"frames": hi - lo, "pixels": int((hi - lo) * SY.H_IMG * SY.W_IMG), "rays": int(len(pool))}
+    if time_pool:     # --full: the pool build itself, timed over three more builds
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            pool = make_pool_rays(*pool_args, **pool_kw)
+        torch.cuda.synchronize(dev)
+        pool_ms = (time.perf_counter() - t0) / 3 * 1e3
+        pool_info.update({"ms": round(pool_ms, 2),
+                          "Mpixel_per_s": round((hi - lo) * SY.H_IMG * SY.W_IMG / pool_ms / 1e3, 1),
+                          "includes": "H2D upload of the frames + 5 HIP launches + n_out readback (make_pool_rays)"})
     counts = torch.bincount(pool[:, 8].long() - lo, minlength=hi - lo).cpu().numpy()
     frame_start = np.cumsum(np.concatenate([[0], counts]))
     return cfg, pool, frame_start, poses_n.astype(np.float32), occ, pool_info, (pool_args, pts, level)
@@ -251,21 +260,26 @@ def cpu_pool_baseline(pool_src, occ, threads, frames=2):
 
 
 def rounds_for(steps_req, n_iters):
-    """The timed region is whole training rounds: bundlesdf.py re-creates the model for
+    """The timed region follows the training rounds: bundlesdf.py re-creates the model for
     every online round (add_new_frames(reuse_weights=False) -> create_nerf, bundlesdf.py:223,
     nerf_runner.py:379-380) and trains n_step + 1 steps (nerf_runner.py:854-862). The step
     cost depends on the training state (work with exactly zero gradient is skipped), so the
-    representative figure is the mean over a whole round from initialisation."""
-    n = max(1, -(-int(steps_req) // n_iters)) if steps_req else 1
-    return n, n * n_iters
+    default is one whole round from initialisation. --steps K times exactly K steps: whole
+    rounds, each from the initial parameters, then the first K mod n_iters steps of one more.
+    Returns (rounds started, timed steps)."""
+    steps = int(steps_req) if steps_req else n_iters
+    if steps < 1:
+        raise SystemExit(f"--steps {steps_req}: need at least 1")
+    return -(-steps // n_iters), steps
 
 
-def run_steps(step_fn, fs, P0, warmup, n_rounds, n_iters, world, dev, phases=()):
+def run_steps(step_fn, fs, P0, warmup, steps, n_iters, world, dev, phases=()):
     """W untimed warm-up steps (graph capture, caches), then the model is re-initialised
-    and EXACTLY n_rounds x n_iters steps are timed between barrier + synchronize on both
-    sides, each round from the initial parameters (fs.reset_state). Returns (max-over-ranks
-    seconds, warm-up s, host enqueue s, last output, phase ms/step over `phases` — step
-    boundaries of the first round, from HIP events on the step stream)."""
+    and EXACTLY `steps` steps are timed between barrier + synchronize on both sides, in
+    rounds of n_iters steps (the last one may be partial), each round from the initial
+    parameters (fs.reset_state). Returns (max-over-ranks seconds, warm-up s, host enqueue s,
+    last output, phase ms/step over `phases` — step boundaries of the first round, from HIP
+    events on the step stream)."""
     torch.cuda.synchronize()
     t_w = time.perf_counter()
     for it in range(warmup):
@@ -276,7 +290,8 @@ def run_steps(step_fn, fs, P0, warmup, n_rounds, n_iters, world, dev, phases=())
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    bounds = sorted(set([0] + [b for b in phases if 0 < b < n_iters] + [n_iters]))
+    n_rounds, n_first = -(-steps // n_iters), min(steps, n_iters)
+    bounds = sorted(set([0] + [b for b in phases if 0 < b < n_first] + [n_first]))
     evs = {}
     t0 = time.perf_counter()
     out = None
@@ -284,7 +299,7 @@ def run_steps(step_fn, fs, P0, warmup, n_rounds, n_iters, world, dev, phases=())
     for rd in range(n_rounds):
         if rd:
             fs.reset_state(P0)
-        for k in range(n_iters):
+        for k in range(min(n_iters, steps - rd * n_iters)):
             if rd == 0 and k in bounds:
                 evs[k] = torch.cuda.Event(enable_timing=True)
                 evs[k].record()
@@ -293,8 +308,8 @@ def run_steps(step_fn, fs, P0, warmup, n_rounds, n_iters, world, dev, phases=())
             if k % 100 == 99:
                 log(f"  round {rd} step {k + 1}/{n_iters}")   # progress (no device sync)
         if rd == 0:
-            evs[n_iters] = torch.cuda.Event(enable_timing=True)
-            evs[n_iters].record()
+            evs[n_first] = torch.cuda.Event(enable_timing=True)
+            evs[n_first].record()
     t_enq = time.perf_counter() - t0
     torch.cuda.synchronize()
     if world > 1:
@@ -333,7 +348,7 @@ def host_cpu():
             "thread_share": share}
 
 
-def side_line(cfg_over, frames, rays_per_frame, dev, warmup, n_rounds, parity=False, amp=True, graph=True):
+def side_line(cfg_over, frames, rays_per_frame, dev, warmup, parity=False, amp=True, graph=True):
     """A single-GPU measurement of another BASELINE configuration (fresh scene,
     fresh models, same protocol): config 2 (16-frame pool), parity mode
     (NerfRunner.train()'s N_rand rays drawn uniformly over the pool), config 1."""
@@ -359,8 +374,8 @@ def side_line(cfg_over, frames, rays_per_frame, dev, warmup, n_rounds, parity=Fa
             step_fn = lambda it: fs.step(ids=fs.sample_ids(rays_per_frame, seed=7000 + it))  # noqa: E731
     n_iters = cfg["n_step"] + 1
     P0 = fs.P.detach().clone()
-    dt, t_w, _, out, prof = run_steps(step_fn, fs, P0, warmup, n_rounds, n_iters, 1, dev, phases=(20, 100))
-    steps = n_rounds * n_iters
+    steps = n_iters                               # one whole round
+    dt, t_w, _, out, prof = run_steps(step_fn, fs, P0, warmup, steps, n_iters, 1, dev, phases=(20, 100))
     ms = dt / steps * 1e3
     e = {"value": round(R * steps / dt, 1), "unit": "rays/s", "ms_per_step": round(ms, 4), "rays_per_step": R,
          "steps": steps, "execution": "hipGraph replay" if graph else "eager launches",
@@ -440,15 +455,128 @@ def dry_run(world, rank):
         torch.distributed.destroy_process_group()
 
 
+def dump_outputs(out_dir, out, rank):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 DIR/<name>.npy:
+    loss_terms (the 8 accumulated loss terms and sample counters) and fs_rgb_loss.
+    The scene, the initial model and every batch draw are seeded, so the same arguments train on
+    the same inputs from run to run; the terms still differ in their last digits between two runs
+    of one build (2 runs of 20 steps: 5e-5 relative), because the fp16 table gradient is
+    accumulated by atomics in no fixed order. The trained parameters are state, not an output of
+    the step, and are left out: Adam turns that rounding noise into whole updates of table entries
+    whose gradient is near zero (the same two runs: entries up to 0.044 apart)."""
+    arrays = {"loss_terms": out["loss_terms"], "fs_rgb_loss": out["fs_rgb_loss"].reshape(1)}
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def full_report(args, fs, P0, fns, n_iters, world, dev, R_local):
+    """--full: the other execution mode over one more round, then the kernel-timing round behind
+    the per-kernel, roofline and MFMA figures. Returns the result line's extra entries."""
+    ids_fn, eager_fn, graph_fn = fns
+    use_graph = not args.no_graph
+    gr = args.workload == "global_refine"
+    # the other execution mode over one more whole round from initialisation
+    dt_o, _, t_enq_o, _, _ = run_steps(eager_fn if use_graph else graph_fn, fs, P0, 0, n_iters, n_iters, world, dev)
+    other = {"execution": "eager launches" if use_graph else "hipGraph replay",
+             "ms_per_step": round(dt_o / n_iters * 1e3, 3), "steps": n_iters,
+             "value": round(world * R_local * n_iters / dt_o, 1),
+             "host_enqueue_ms_per_step": round(t_enq_o / n_iters * 1e3, 3)}
+    # ---- kernel-timing pass: one more whole round (eager launches from initialisation) with
+    # HIP events recorded between the field kernels on their stream
+    fs.reset_state(P0)
+    fs.time_kernels = True
+    n_valid = torch.zeros(1, device=dev)
+    n_bwd = torch.zeros(1, device=dev)
+    n_atom = torch.zeros(2, device=dev)
+    for it in range(n_iters):
+        out = fs.step(ids=ids_fn(it))
+        if it % 100 == 99:
+            log(f"  kernel-timing round step {it + 1}/{n_iters}")
+        n_valid += out["loss_terms"][4]
+        n_bwd += out["loss_terms"][5]
+        n_atom += fs.scatter_atomic_counts()
+    torch.cuda.synchronize()
+    kms = fs.field_kernel_ms()
+    k_ms = float(np.mean(kms))
+    br, n_calls = fs.field_kernel_breakdown()
+    fs.time_kernels = False
+    nv = float(n_valid.item()) / n_iters
+    nb = float(n_bwd.item()) / n_iters
+    n_rec = float(fs.n_tile_records())
+    # algorithmic bytes per launch of each kernel (SURVEY §8d per-unit figures x units of one launch)
+    alg = {"k_encode": nv * ENC_FWD_B, "k_scatter": nb * GRID_BWD_B}
+    kernels = {}
+    for name, kms_k in br.items():
+        e = {"ms": round(kms_k, 4)}
+        if name in alg and kms_k > 0:
+            e["achieved_GBs"] = round(alg[name] / (kms_k * 1e-3) / 1e9, 1)
+        kernels[name] = e
+    if "achieved_GBs" in kernels.get("k_encode", {}):
+        # the encode's corner gathers are served from L2 / Infinity Cache, not HBM (its PMC traffic is
+        # far below the algorithmic bytes): its ceiling is the cache tier's (L2_SHARED_GATHER_GBS, gathers
+        # of L2-shared rows), not the HBM peak
+        ke = kernels["k_encode"]
+        ke["cache_tier"] = {"ceiling_GBs": L2_SHARED_GATHER_GBS, "frac": round(ke["achieved_GBs"] / L2_SHARED_GATHER_GBS, 4),
+                            "note": "algorithmic bytes / duration vs the L2-shared-row gather ceiling (16.8 TB/s; "
+                                    "random Infinity-Cache gathers: 8.6 TB/s)"}
+    dom = max((k for k in alg), key=lambda k: br[k])
+    achieved = alg[dom] / (br[dom] * 1e-3) / 1e9
+    per_unit = {"k_encode": f"{ENC_FWD_B} B/in-box sample (§8d encode fwd, fp16 table)",
+                "k_scatter": f"{GRID_BWD_B} B/backward sample (§8d grid bwd, fp16 table + fp16 gradient RMW)"}[dom]
+    traffic, traffic_src = pmc_traffic(dom, args.workload, args.frames_per_gpu) if not gr else \
+        (None, "no PMC pass committed for this workload")
+    # MLP on MFMA (north_star: MFMA utilisation against the gfx950 peak): the headline figure
+    # counts the FLOPs the kernels executed (tile counters, unpadded); the reference-FLOP
+    # figure (every in-box sample runs forward + full backward, 3 x 17,792 FLOP, §8d) beside it
+    mlp_ms = sum(br.get(k, 0.0) for k in MLP_KERNELS)
+    mlp_tf = nv * 3 * MLP_FWD_FLOP / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
+    ex = executed_mlp_flops(fs, mlp_ms)
+    mlp = {"kernels": list(MLP_KERNELS), "ms": round(mlp_ms, 4), "achieved": ex["achieved"],
+           "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ex["frac"], "executed": ex,
+           "reference_flops": {"alg_flop_per_sample": 3 * MLP_FWD_FLOP, "achieved": round(mlp_tf, 1),
+                               "frac": round(mlp_tf / MFMA_F16_PEAK_TFLOPS, 4),
+                               "note": "reference FLOPs of every in-box sample, including tiles this "
+                                       "implementation skips (zero gradient)"},
+           "pmc_mfma_busy": None if gr else pmc_mfma(args.workload, args.frames_per_gpu)}
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "traffic": traffic, "traffic_source": traffic_src, "alg_bytes": int(alg[dom]),
+                     "kernel_ms": round(br[dom], 4), "per_unit": per_unit,
+                     "units_per_launch": int({"k_encode": nv, "k_scatter": nb}[dom]),
+                     "timed_calls": n_calls,
+                     "timing": "HIP events between the field kernels over one whole round (501 eager steps from "
+                               "initialisation, same workload) after the timed region; value/ms_per_step come "
+                               "from the uninstrumented pass"},
+        "other_execution": other,
+        "field_step_ms": round(k_ms, 3),
+        "kernels": kernels,
+        "mlp_mfma": mlp,
+        "samples_in_box": int(nv), "samples_backward": int(nb), "tile_records": int(n_rec),
+        "scatter_hbm_atomics": {"table_flush": int(n_atom[0].item() / n_iters),
+                                "probe_overflow": int(n_atom[1].item() / n_iters)},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (no GPU): CPU tests")
-    # the timed region is whole training rounds of n_step + 1 = 501 steps (config.yml n_step),
-    # each from a freshly initialised model (rounds_for): --steps K times ceil(K / 501) rounds
-    # (default one); W warm-up steps run before and the model is re-initialised after them
+    # the timed region is exactly --steps K steps, laid out as training rounds of n_step + 1 = 501
+    # steps (config.yml n_step), each from a freshly initialised model (rounds_for); default one
+    # whole round. W warm-up steps run before and the model is re-initialised after them
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other execution mode, the per-kernel / "
+                         "roofline / MFMA pass, the ray-pool timing, the config-2 / parity-mode / config-1 "
+                         "lines and the CPU baselines (--no-extras / --no-cpu-baseline drop those two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (dump_outputs) as "
+                         "DIR/<name>.npy")
     # headline (default): BASELINE.json's metric — the 64-frame pool at 2048 rays/frame
     # (131,072 rays per optimiser step), sharded 64/N frames per rank (config 4's strong
     # scaling at fixed R_global); config2: 16 frames per GPU (weak); global_refine: the
@@ -490,8 +618,10 @@ def main():
             args.frames_per_gpu = 63 if gr else 16
     if args.rays_per_frame is None:
         args.rays_per_frame = 4096 if gr else 2048
-    if gr:
-        args.no_cpu_baseline = True   # the CPU port of a 258k-ray x 320-sample step would run for hours
+    if gr or not args.full:
+        # a plain run measures the headline figure only; under global_refine the CPU port of a
+        # 258k-ray x 320-sample step would run for hours
+        args.no_cpu_baseline = True
         args.no_extras = True
 
     # NOF_BENCH_BACKEND=gloo + NOF_BENCH_SHARE_GPU=1: rehearsal of the N-rank path on
@@ -509,7 +639,7 @@ def main():
     t_setup = time.time()
     cfg, pool, frame_start, c2w, occ, pool_info, pool_src = build_rank_scene(rank, world, args.frames_per_gpu,
                                                                              dict(amp=True, **(GLOBAL_REFINE if gr else {})),
-                                                                             dev)
+                                                                             dev, time_pool=args.full)
     F_total = args.frames_per_gpu * world
     enc, net, pa, fa = make_models(cfg, F_total, dev, with_features=True)
     fs = FusedStep(cfg, pool, torch.from_numpy(c2w), occ, enc, net, pa, amp=True,
@@ -532,74 +662,15 @@ def main():
     n_rounds, steps = rounds_for(args.steps, n_iters)
     P0 = fs.P.detach().clone()            # the round's initial parameters (create_nerf)
     use_graph = not args.no_graph
-    dt, t_w, t_enq, out, phases = run_steps(graph_fn if use_graph else eager_fn, fs, P0, args.warmup, n_rounds,
+    dt, t_w, t_enq, out, phases = run_steps(graph_fn if use_graph else eager_fn, fs, P0, args.warmup, steps,
                                             n_iters, world, dev, phases=(20, 100))
     ms = dt / steps * 1e3
     value = world * R_local * steps / dt
     loss = float(out["loss_terms"][:4].sum().item())
-    # the other execution mode over one more whole round from initialisation
-    dt_o, _, t_enq_o, _, _ = run_steps(eager_fn if use_graph else graph_fn, fs, P0, 0, 1, n_iters, world, dev)
-    other = {"execution": "eager launches" if use_graph else "hipGraph replay",
-             "ms_per_step": round(dt_o / n_iters * 1e3, 3), "steps": n_iters,
-             "value": round(world * R_local * n_iters / dt_o, 1),
-             "host_enqueue_ms_per_step": round(t_enq_o / n_iters * 1e3, 3)}
-    # ---- kernel-timing pass: one more whole round (eager launches from initialisation) with
-    # HIP events recorded between the field kernels on their stream
-    fs.reset_state(P0)
-    fs.time_kernels = True
-    n_valid = torch.zeros(1, device=dev)
-    n_bwd = torch.zeros(1, device=dev)
-    n_atom = torch.zeros(2, device=dev)
-    for it in range(n_iters):
-        out = fs.step(ids=ids_fn(it))
-        if it % 100 == 99:
-            log(f"  kernel-timing round step {it + 1}/{n_iters}")
-        n_valid += out["loss_terms"][4]
-        n_bwd += out["loss_terms"][5]
-        n_atom += fs.scatter_atomic_counts()
-    torch.cuda.synchronize()
-    kms = fs.field_kernel_ms()
-    k_ms = float(np.mean(kms))
-    br, n_calls = fs.field_kernel_breakdown()
-    fs.time_kernels = False
-    nv = float(n_valid.item()) / n_iters
-    nb = float(n_bwd.item()) / n_iters
-    n_rec = float(fs.n_tile_records())
-    # algorithmic bytes per launch of each kernel (SURVEY §8d per-unit figures x units of one launch)
-    alg = {"k_encode": nv * ENC_FWD_B, "k_scatter": nb * GRID_BWD_B}
-    kernels = {}
-    for name, kms_k in br.items():
-        e = {"ms": round(kms_k, 4)}
-        if name in alg and kms_k > 0:
-            e["achieved_GBs"] = round(alg[name] / (kms_k * 1e-3) / 1e9, 1)
-        kernels[name] = e
-    if "achieved_GBs" in kernels.get("k_encode", {}):
-        # the encode's corner gathers are served from L2 / Infinity Cache, not HBM (its PMC traffic is
-        # far below the algorithmic bytes): its ceiling is the cache tier's (MI355X_MICROARCH.md, gathers
-        # of L2-shared rows), not the HBM peak
-        ke = kernels["k_encode"]
-        ke["cache_tier"] = {"ceiling_GBs": L2_SHARED_GATHER_GBS, "frac": round(ke["achieved_GBs"] / L2_SHARED_GATHER_GBS, 4),
-                            "note": "algorithmic bytes / duration vs the L2-shared-row gather ceiling (16.8 TB/s; "
-                                    "random Infinity-Cache gathers: 8.6 TB/s)"}
-    dom = max((k for k in alg), key=lambda k: br[k])
-    achieved = alg[dom] / (br[dom] * 1e-3) / 1e9
-    per_unit = {"k_encode": f"{ENC_FWD_B} B/in-box sample (§8d encode fwd, fp16 table)",
-                "k_scatter": f"{GRID_BWD_B} B/backward sample (§8d grid bwd, fp16 table + fp16 gradient RMW)"}[dom]
-    traffic, traffic_src = pmc_traffic(dom, args.workload, args.frames_per_gpu) if not gr else \
-        (None, "no PMC pass committed for this workload")
-    # MLP on MFMA (north_star: MFMA utilisation against the gfx950 peak): the headline figure
-    # counts the FLOPs the kernels executed (tile counters, unpadded); the reference-FLOP
-    # figure (every in-box sample runs forward + full backward, 3 x 17,792 FLOP, §8d) beside it
-    mlp_ms = sum(br.get(k, 0.0) for k in MLP_KERNELS)
-    mlp_tf = nv * 3 * MLP_FWD_FLOP / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
-    ex = executed_mlp_flops(fs, mlp_ms)
-    mlp = {"kernels": list(MLP_KERNELS), "ms": round(mlp_ms, 4), "achieved": ex["achieved"],
-           "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ex["frac"], "executed": ex,
-           "reference_flops": {"alg_flop_per_sample": 3 * MLP_FWD_FLOP, "achieved": round(mlp_tf, 1),
-                               "frac": round(mlp_tf / MFMA_F16_PEAK_TFLOPS, 4),
-                               "note": "reference FLOPs of every in-box sample, including tiles this "
-                                       "implementation skips (zero gradient)"},
-           "pmc_mfma_busy": None if gr else pmc_mfma(args.workload, args.frames_per_gpu)}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
+    fns = (ids_fn, eager_fn, graph_fn)
+    full = full_report(args, fs, P0, fns, n_iters, world, dev, R_local) if args.full else {}
     if gr:
         workload = ("BASELINE config 5 (global refine) per-GPU shape: 63-frame pool/GPU, 4096 rays/frame, "
                     "320 samples/ray (64 + 256 around depth), L=16 hash grid (finest 256, 2^22, top levels "
@@ -627,53 +698,39 @@ def main():
                                       "fp16 table mirror, all-reduce of the MLP/feature/pose bucket)"
                                       if fs.exchange == "sharded" else "fp32 gradient all-reduce)")
                                    if world > 1 else "single GPU")},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "traffic_source": traffic_src, "alg_bytes": int(alg[dom]),
-                     "kernel_ms": round(br[dom], 4), "per_unit": per_unit,
-                     "units_per_launch": int({"k_encode": nv, "k_scatter": nb}[dom]),
-                     "timed_calls": n_calls,
-                     "timing": "HIP events between the field kernels over one whole round (501 eager steps from "
-                               "initialisation, same workload) after the timed region; value/ms_per_step come "
-                               "from the uninstrumented pass"},
-        "timed_region": (f"{n_rounds} whole training round(s) of n_step + 1 = {n_iters} steps, each from a freshly "
-                         "initialised model (bundlesdf.py:223 re-creates it every online round); the W warm-up "
-                         "steps run before and are followed by a re-initialisation"),
+        "timed_region": (f"{steps} steps in {n_rounds} training round(s) of at most n_step + 1 = {n_iters} steps, each "
+                         "from a freshly initialised model (bundlesdf.py:223 re-creates it every online round); the "
+                         "W warm-up steps run before and are followed by a re-initialisation"),
         "steps_requested": args.steps,
-        "steps_policy": (f"whole training rounds: steps = ceil(steps_requested / {n_iters}) x {n_iters} (one round "
-                         "when --steps is not given), never fewer than requested. A round starts from a freshly "
-                         "initialised model, as bundlesdf.py re-creates it every online round, and its per-step "
-                         "cost changes over the round (round_phases_ms_per_step), so a partial round would not "
-                         "measure the reference's training step"),
+        "steps_policy": (f"steps = steps_requested exactly (one whole round of {n_iters} when --steps is not given): "
+                         f"whole rounds, then the first steps_requested mod {n_iters} steps of one more. A round "
+                         "starts from a freshly initialised model, as bundlesdf.py re-creates it every online "
+                         "round, and its per-step cost changes over the round (round_phases_ms_per_step), so only "
+                         f"a multiple of {n_iters} steps measures the reference's whole training round"),
         "round_phases_ms_per_step": phases,
         "execution": "hipGraph replay (one captured graph per step: schedule, batch draw, field pass, "
                      "optimiser)" if use_graph else "eager launches",
-        "other_execution": other,
         "warmup_ms_per_step": round(t_w / max(args.warmup, 1) * 1e3, 3) if args.warmup else None,
-        "field_step_ms": round(k_ms, 3),
         # graph mode: the host waits for the replay GRAPH_INFLIGHT steps back, so its loop time
-        # tracks the GPU; the eager pass's enqueue time is in other_execution
+        # tracks the GPU; under --full the eager pass's enqueue time is in other_execution
         "host_enqueue_ms_per_step": None if use_graph else round(t_enq / steps * 1e3, 3),
-        "kernels": kernels,
-        "mlp_mfma": mlp,
-        "samples_in_box": int(nv), "samples_backward": int(nb), "tile_records": int(n_rec),
-        "scatter_hbm_atomics": {"table_flush": int(n_atom[0].item() / n_iters),
-                                "probe_overflow": int(n_atom[1].item() / n_iters)},
         "loss": round(loss, 5),
         "ray_pool": pool_info,
+        "full": args.full,
     }
+    result.update(full)
     del fs
     torch.cuda.empty_cache()
     if rank == 0 and world == 1 and not args.no_extras:
         # other BASELINE configurations, same protocol (fresh scene + models each)
-        result["config2"], _ = side_line({}, 16, 2048, dev, args.warmup, 1)
+        result["config2"], _ = side_line({}, 16, 2048, dev, args.warmup)
         result["config2"]["workload"] = "BASELINE config 2: 16-frame pool, 2048 rays/frame (32,768 rays/step), amp"
-        result["parity_mode"], _ = side_line({}, args.pool_frames, 2048, dev, args.warmup, 1, parity=True)
+        result["parity_mode"], _ = side_line({}, args.pool_frames, 2048, dev, args.warmup, parity=True)
         result["parity_mode"]["workload"] = (f"NerfRunner.train() semantics: N_rand=2048 rays per step drawn by the "
                                              f"epoch randperm over the whole {args.pool_frames}-frame pool, amp")
-        pe, _ = side_line({}, args.pool_frames, 2048, dev, args.warmup, 1, parity=True, graph=False)
+        pe, _ = side_line({}, args.pool_frames, 2048, dev, args.warmup, parity=True, graph=False)
         result["parity_mode"]["eager"] = {k: pe[k] for k in ("value", "ms_per_step", "execution")}
-        c1, (cfg1, pool1, c2w1, occ1) = side_line(dict(num_levels=4), 1, 512, dev, args.warmup, 1,
+        c1, (cfg1, pool1, c2w1, occ1) = side_line(dict(num_levels=4), 1, 512, dev, args.warmup,
                                                   amp=False)
         c1["workload"] = "BASELINE config 1: 1 frame, 512 rays/step, 192 samples/ray, L=4 (config.yml), fp32"
         if not args.no_cpu_baseline:

@@ -1,12 +1,13 @@
 set -o pipefail
-R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${NOF_OUT_DIR:-$R/out}   # results directory (NOF_OUT_DIR overrides)
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="--warmup 20 --no-cpu-baseline --no-extras"
-timeout -s KILL 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_LDS --kernel-include-regex "k_colour|k_mlp_bwd_tr" --output-format csv -d $R/gpurun_out/pmc_col -o run -- python $R/bench.py $CMD > $R/gpurun_out/pmc_col.log 2>&1 || { tail -20 $R/gpurun_out/pmc_col.log; exit 4; }
-cd $R && python - <<'PY'
+CMD="--full --warmup 20 --no-cpu-baseline --no-extras"
+timeout -s KILL 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_LDS --kernel-include-regex "k_colour|k_mlp_bwd_tr" --output-format csv -d $OUT/pmc_col -o run -- python $R/bench.py $CMD > $OUT/pmc_col.log 2>&1 || { tail -20 $OUT/pmc_col.log; exit 4; }
+cd $R && python - <<PY
 import csv, glob, collections
-f = glob.glob("gpurun_out/pmc_col/**/*counter_collection.csv", recursive=True)[0]
+f = glob.glob("$OUT/pmc_col/**/*counter_collection.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for r in rows:

@@ -2,12 +2,13 @@
 # for each "VAR=VALUE ..." set given as an argument (one process each). Usage:
 #   bash scripts/gpu_small_sweep.sh TAG "" "LPW=1" "SLOTS=256" ...
 set -o pipefail
-R=$GRAFT_REPO_ROOT
-cd $R && mkdir -p gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${NOF_OUT_DIR:-$R/out}   # results directory (NOF_OUT_DIR overrides)
+cd $R && mkdir -p $OUT
 TAG=${1:?tag}
 shift
 for v in "$@"; do
-  env $v timeout -k 10 240 python scripts/small_batch_prof.py 300 >> gpurun_out/small_sweep_$TAG.txt 2> gpurun_out/small_sweep_$TAG.err \
-    || { tail -20 gpurun_out/small_sweep_$TAG.err; exit 1; }
+  env $v timeout -k 10 240 python scripts/small_batch_prof.py 300 >> $OUT/small_sweep_$TAG.txt 2> $OUT/small_sweep_$TAG.err \
+    || { tail -20 $OUT/small_sweep_$TAG.err; exit 1; }
 done
-cat gpurun_out/small_sweep_$TAG.txt
+cat $OUT/small_sweep_$TAG.txt

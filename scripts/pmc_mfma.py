@@ -33,7 +33,7 @@ def main():
     ap.add_argument("csv")
     ap.add_argument("out")
     ap.add_argument("--last", type=int, default=10)
-    ap.add_argument("--cmd", default="bench.py --steps 10 --warmup 20 --no-cpu-baseline --no-extras")
+    ap.add_argument("--cmd", default="bench.py --full --steps 10 --warmup 20 --no-cpu-baseline --no-extras")
     ap.add_argument("--workload", default="headline:64")
     a = ap.parse_args()
     # per (kernel, template instance): a kernel launched as several instances per step

@@ -3,12 +3,14 @@ output, over the last N dispatches. Usage: python scripts/pmc_sq_summary.py TAG 
 import collections
 import csv
 import glob
+import os
 import sys
 
 tag = sys.argv[1]
 last = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+out_dir = os.environ.get("NOF_OUT_DIR") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "out")
 vals = collections.defaultdict(lambda: collections.defaultdict(list))
-for f in glob.glob(f"gpurun_out/pmc_sq[12]_{tag}/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(f"{out_dir}/pmc_sq[12]_{tag}/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         vals[r["Kernel_Name"][:60]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, c in vals.items():

@@ -31,7 +31,7 @@ def main():
     ap.add_argument("write_csv")
     ap.add_argument("out")
     ap.add_argument("--last", type=int, default=10)
-    ap.add_argument("--cmd", default="bench.py --steps 10 --warmup 20 --no-cpu-baseline --no-extras")
+    ap.add_argument("--cmd", default="bench.py --full --steps 10 --warmup 20 --no-cpu-baseline --no-extras")
     ap.add_argument("--workload", default="headline:64", help="bench workload:frames_per_gpu the passes ran")
     a = ap.parse_args()
     f, w = load(a.fetch_csv, a.last), load(a.write_csv, a.last)
