@@ -40,6 +40,7 @@ _SIGNATURES = {
     "nof_sample_batch": ([_p, _i32, _i32, _u32, _p, _p, _p], _int),
     "nof_pack_mlp": ([_p, _p, _i32, _i32, _p, _p, _int, _p], _int),
     "nof_field_step": ([_p, _p], _int),
+    "nof_field_desc_size": ([], ctypes.c_size_t),
     "nof_quad_mirror": ([_p, _p], _int),
     "nof_field_workspace_bytes": ([_i32, _i32, _i32], ctypes.c_size_t),
     "nof_field_workspace_offsets": ([_i32, _i32, _i32, _p, _i32], _int),
@@ -73,25 +74,27 @@ _SIGNATURES = {
 
 
 class FieldDesc(ctypes.Structure):
-    """Mirror of nof_field_desc (include/nof.h)."""
-    _fields_ = [("rays", _p), ("tf", _p), ("intervals", _p), ("totals", _p), ("t_rand", _p), ("seed", _u32),
+    """Mirror of nof_field_desc (include/nof.h), in the header's order and sections."""
+    _fields_ = [# batch inputs and scalars
+                ("rays", _p), ("tf", _p), ("intervals", _p), ("totals", _p), ("t_rand", _p), ("seed", _u32),
                 ("R", _i32), ("Kmax", _i32), ("N_oct", _i32), ("N_dep", _i32), ("S", _i32), ("perturb", _i32),
                 ("near_sc", _f32), ("far_sc", _f32), ("trunc", _f32), ("neg_trunc_ratio", _f32), ("sdf_lambda", _f32),
                 ("fs_sdf", _f32), ("first_frame_weight", _f32), ("rgb_weight", _f32), ("fs_weight", _f32),
-                ("empty_weight", _f32), ("trunc_weight", _f32), ("loss_scale", _p), ("table", _p), ("levels", _p),
-                ("L", _u32), ("C", _u32), ("D", _u32), ("table_dtype", _i32), ("mlp_dtype", _i32), ("frags", _p),
-                ("bias", _p), ("grad_table", _p), ("grad_table16", _p), ("grad_mlp", _p), ("ray_grad", _p), ("loss_acc", _p), ("dbg_z", _p),
-                ("dbg_raw", _p), ("dbg_valid", _p), ("dbg_rgb", _p), ("blocks_per_cu", _i32), ("ablate", _i32),
-                ("workspace", _p), ("scatter_slots", _i32),
-                ("n_ff", _i32), ("ff", _p), ("grad_ff", _p), ("fs_rgb_weight", _f32),
-                ("xcd_order", _i32), ("step_params", _p), ("skip_pose_grad", _i32),
-                ("scatter_levels_per_wave", _i32), ("table_quads", _p),
-                ("table_rows", ctypes.c_int64), ("quads_min_rays", _i32), ("scatter_kernel", _i32),
-                ("scatter_waves_per_ray", _i32), ("scatter_ls_levels", _i32), ("encode_sigma", _i32),
-                ("bwd_flush", _i32), ("count_atomics", _i32),
-                ("scatter_flat", _i32), ("compact_per_block", _i32),
-                ("encode_group", _i32), ("quads_prebuilt", _i32), ("mlp_pass1_tiles", _i32),
-                ("scatter_fuse_levels", _i32), ("encode_wpb", _i32)]
+                ("empty_weight", _f32), ("trunc_weight", _f32), ("fs_rgb_weight", _f32), ("skip_pose_grad", _i32),
+                ("loss_scale", _p), ("step_params", _p),
+                # parameters
+                ("table", _p), ("levels", _p), ("L", _u32), ("C", _u32), ("D", _u32), ("table_dtype", _i32),
+                ("mlp_dtype", _i32), ("n_ff", _i32), ("frags", _p), ("bias", _p), ("ff", _p),
+                # outputs
+                ("grad_table", _p), ("grad_table16", _p), ("grad_mlp", _p), ("grad_ff", _p), ("ray_grad", _p),
+                ("loss_acc", _p),
+                # debug outputs
+                ("dbg_z", _p), ("dbg_raw", _p), ("dbg_valid", _p), ("dbg_rgb", _p),
+                # workspace
+                ("workspace", _p), ("table_quads", _p), ("table_rows", _i64), ("quads_prebuilt", _i32),
+                # shape knobs
+                ("count_atomics", _i32), ("ablate", _i32), ("scatter_slots", _i32), ("scatter_levels_per_wave", _i32), ("bwd_flush", _i32),
+                ("compact_per_block", _i32), ("encode_group", _i32), ("quads_min_rays", _i32), ("xcd_order", _i32)]
 
 
 class StepParams(ctypes.Structure):
@@ -123,14 +126,30 @@ def declared_symbols():
     return list(_SIGNATURES)
 
 
+def check_field_desc_layout(L, struct=FieldDesc):
+    """Raise unless library L was built from the nof_field_desc that `struct` mirrors: a library
+    from another header (NOF_LIB, a stale libnof_prev.so / libnof_ablate.so) would read the
+    descriptor's pointers from the wrong offsets."""
+    fn = getattr(L, "nof_field_desc_size", None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} does not export nof_field_desc_size: it predates this binding's "
+                           f"nof_field_desc ({ctypes.sizeof(struct)} bytes) — rebuild it")
+    fn.argtypes, fn.restype = _SIGNATURES["nof_field_desc_size"]
+    if fn() != ctypes.sizeof(struct):
+        raise RuntimeError(f"{LIB_PATH}: nof_field_desc is {fn()} bytes in the library, {ctypes.sizeof(struct)} "
+                           "in this binding — rebuild the library from the current include/nof.h")
+
+
 def lib():
-    """Load libnof.so once; raise if it is missing (no fallback)."""
+    """Load libnof.so once; raise if it is missing (no fallback) or built from another
+    nof_field_desc than FieldDesc mirrors."""
     global _LIB
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m bundlesdf_amd.build` "
                                "(the HIP path has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+        check_field_desc_layout(L)
         for name, (args, res) in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = args

@@ -2715,7 +2715,17 @@ bool quads_on(const nof_field_desc *d) {
     return d->table_quads && d->table_rows > 0 && d->mlp_dtype == NOF_F16 && d->table_dtype == NOF_F16 &&
            d->R >= (d->quads_min_rays > 0 ? d->quads_min_rays : 32768) && !ABL_HOST(d, 512);
 }
+// compute units of the current device (the persistent grids' size); 256, the MI355X's, when the query fails
+int cu_count() {
+    int dev = 0, n_cu = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        n_cu = 256;
+    return n_cu;
+}
 }  // namespace
+
+extern "C" size_t nof_field_desc_size(void) { return sizeof(nof_field_desc); }
 
 extern "C" int nof_quad_mirror(const nof_field_desc *d, void *stream) {
     if (d->L > 16 || d->C != 2)
@@ -2724,10 +2734,7 @@ extern "C" int nof_quad_mirror(const nof_field_desc *d, void *stream) {
     nof::FieldArgs a{};
     a.table = d->table; a.levels = (const float4 *)d->levels; a.L = d->L;
     a.quads = (const uint4 *)d->table_quads; a.n_rows = (uint32_t)d->table_rows;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        n_cu = 256;
+    const int n_cu = cu_count();
     hipLaunchKernelGGL(nof::k_quad_mirror, dim3((int)std::min<int64_t>((int64_t)n_cu * 8, nof::div_up(a.n_rows, 256))),
                        dim3(256), 0, (hipStream_t)stream, a);
     return nof::check_launch("quad_mirror");
@@ -2739,6 +2746,30 @@ extern "C" int nof_field_step(const nof_field_desc *d, void *stream) {
     if (d->L > 16 || d->C != 2 || d->D != 3)
         return nof::set_error(NOF_EINVAL, "field_step: needs D=3, C=2, L<=16 (got %u,%u,%u)", d->D, d->C, d->L);
     if (d->R <= 0) return NOF_OK;
+    // every refusal comes before the first HIP call: a bad descriptor costs no device work
+    if (d->bwd_flush < 0 || d->bwd_flush > 2)
+        return nof::set_error(NOF_EINVAL, "field_step: bwd_flush %d (0 by batch size, 1 per wave, 2 block)", d->bwd_flush);
+    if (d->compact_per_block != 0 && (d->compact_per_block < 256 || d->compact_per_block > nof::COMPACT_PER_BLOCK ||
+                                      d->compact_per_block % 256 != 0))
+        return nof::set_error(NOF_EINVAL, "field_step: compact_per_block %d (0 by batch size, else a multiple of 256 "
+                              "in [256, %d])", d->compact_per_block, nof::COMPACT_PER_BLOCK);
+    if (d->encode_group != 0 && d->encode_group != 1 && d->encode_group != 2 && d->encode_group != 4)
+        return nof::set_error(NOF_EINVAL, "field_step: encode_group %d (0 by batch size, or 1, 2, 4)", d->encode_group);
+    if (d->n_ff < 0 || d->n_ff > 3 || (d->n_ff > 0 && (!d->ff || !d->grad_ff)))
+        return nof::set_error(NOF_EINVAL, "field_step: frame_features must be 0..3 with ff and grad_ff set (got %d)",
+                              d->n_ff);
+    if (d->mlp_dtype == NOF_F16 && !d->grad_table16)
+        return nof::set_error(NOF_EINVAL, "field_step: amp mode needs grad_table16 (fp16 table gradient)");
+    if (d->ablate && !NOF_ABLATE)
+        return nof::set_error(NOF_EINVAL, "field_step: ablate bits need a -DNOF_ABLATE=1 build (timing experiments only)");
+    if (!d->workspace) return nof::set_error(NOF_EINVAL, "field_step: workspace is NULL (nof_field_workspace_bytes)");
+    const int slots = d->scatter_slots ? d->scatter_slots : 512;
+    if (slots < 64 || slots > 2048 || (slots & (slots - 1)))
+        return nof::set_error(NOF_EINVAL, "field_step: scatter_slots must be a power of two in [64, 2048]");
+    const bool amp = d->mlp_dtype == NOF_F16 && d->table_dtype == NOF_F16;
+    if (!amp && !(d->mlp_dtype == NOF_F32 && d->table_dtype == NOF_F32))
+        return nof::set_error(NOF_EINVAL, "field_step: mlp/table dtype must both be f16 (amp) or both f32");
+
     nof::FieldArgs a;
     a.rays = d->rays; a.tf = d->tf; a.intervals = d->intervals; a.totals = d->totals; a.t_rand = d->t_rand;
     a.seed = d->seed; a.R = d->R; a.Kmax = d->Kmax; a.N_oct = d->N_oct; a.N_dep = d->N_dep; a.S = d->S;
@@ -2761,62 +2792,24 @@ extern "C" int nof_field_step(const nof_field_desc *d, void *stream) {
         // 2048 rays: 0.418 -> 0.395 ms per step vs 1)
         const int L = std::max(1, (int)d->L);
         const int want = d->R >= 196608 ? 16 : (d->R >= 32768 ? 8 : (d->R >= 8192 ? 4 : 2));
-        a.scatter_lpw = std::min(L, d->scatter_levels_per_wave > 0 ? (int)d->scatter_levels_per_wave : want);
-        // the scatter_kernel values 1 (level-serial) and 3 (hybrid) and scatter_flat 1 were measured slower
-        // at every batch size and removed: only the run-scan k_scatter remains
-        // scatter_kernel 1 (level-serial), 3 (hybrid) and 4 (paired: two list entries per lane, two levels per
-        // iteration) were measured slower and removed: only the run-scan k_scatter remains
-        if (d->scatter_kernel != 0 && d->scatter_kernel != 2)
-            return nof::set_error(NOF_EINVAL, "field_step: scatter_kernel %d (0 / 2: the run-scan scatter; 1, 3 and 4 "
-                                  "were removed)", d->scatter_kernel);
-        if (d->scatter_flat != 0)
-            return nof::set_error(NOF_EINVAL, "field_step: scatter_flat was removed (must be 0)");
-        a.scatter_lpw = std::max(1, a.scatter_lpw);
+        a.scatter_lpw = std::max(1, std::min(L, d->scatter_levels_per_wave > 0 ? (int)d->scatter_levels_per_wave : want));
     }
-    // encode_sigma 2 (sigma net in a per-ray forward kernel) and 3 (per-ray colour forward) were measured no
-    // faster than the default and removed: the sigma net runs in k_encode, the colour net tile-parallel
-    if (d->encode_sigma != 0 && d->encode_sigma != 1)
-        return nof::set_error(NOF_EINVAL, "field_step: encode_sigma %d (0 / 1; 2 and 3 were removed)", d->encode_sigma);
-    if (d->bwd_flush < 0 || d->bwd_flush > 2)
-        return nof::set_error(NOF_EINVAL, "field_step: bwd_flush %d (0 by batch size, 1 per wave, 2 block)", d->bwd_flush);
     a.bwd_flush = d->bwd_flush;
     a.count_atomics = d->count_atomics != 0;
-    if (d->compact_per_block != 0 && (d->compact_per_block < 256 || d->compact_per_block > nof::COMPACT_PER_BLOCK ||
-                                      d->compact_per_block % 256 != 0))
-        return nof::set_error(NOF_EINVAL, "field_step: compact_per_block %d (0 by batch size, else a multiple of 256 "
-                              "in [256, %d])", d->compact_per_block, nof::COMPACT_PER_BLOCK);
     a.compact_per = d->compact_per_block;
-    if (d->encode_group != 0 && d->encode_group != 1 && d->encode_group != 2 && d->encode_group != 4)
-        return nof::set_error(NOF_EINVAL, "field_step: encode_group %d (0 by batch size, or 1, 2, 4)", d->encode_group);
     a.encode_group = d->encode_group ? d->encode_group : (d->R >= 8192 ? 1 : nof::ENCODE_GROUP_SMALL);
-    if (d->mlp_pass1_tiles != 0 && d->mlp_pass1_tiles != 1)
-        return nof::set_error(NOF_EINVAL, "field_step: mlp_pass1_tiles %d (0 / 1; several tiles per wave were "
-                                          "measured slower and removed)", d->mlp_pass1_tiles);
-    if (d->scatter_fuse_levels != 0 && d->scatter_fuse_levels != 1)
-        return nof::set_error(NOF_EINVAL, "field_step: scatter_fuse_levels %d (0 / 1; level-fused scatter chunks "
-                                          "were measured slower and removed)", d->scatter_fuse_levels);
-    if (d->encode_wpb != 0 && d->encode_wpb != 8)
-        return nof::set_error(NOF_EINVAL, "field_step: encode_wpb %d (0 / 8; 16-wave encode blocks were measured "
-                                          "slower and removed)", d->encode_wpb);
     a.sp = d->step_params;
     a.fs_rgb_w = d->fs_rgb_weight;
     a.loss_scale = d->loss_scale; a.table = d->table; a.levels = (const float4 *)d->levels; a.L = d->L;
     a.mlp_in = (int)(d->L * d->C);
-    if (d->n_ff < 0 || d->n_ff > 3 || (d->n_ff > 0 && (!d->ff || !d->grad_ff)))
-        return nof::set_error(NOF_EINVAL, "field_step: frame_features must be 0..3 with ff and grad_ff set (got %d)",
-                              d->n_ff);
     a.n_ff = d->n_ff; a.ff = d->ff; a.grad_ff = d->grad_ff;
     a.frags = d->frags; a.bias = d->bias; a.grad_table = d->grad_table; a.grad_mlp = d->grad_mlp;
     a.grad_table16 = (__half *)d->grad_table16;
-    if (d->mlp_dtype == NOF_F16 && !d->grad_table16)
-        return nof::set_error(NOF_EINVAL, "field_step: amp mode needs grad_table16 (fp16 table gradient)");
     a.ray_grad = d->ray_grad; a.loss_acc = d->loss_acc; a.dbg_z = d->dbg_z; a.dbg_raw = d->dbg_raw;
     a.dbg_valid = d->dbg_valid; a.dbg_rgb = d->dbg_rgb; a.ablate = d->ablate;
-    if (d->ablate && !NOF_ABLATE)
-        return nof::set_error(NOF_EINVAL, "field_step: ablate bits need a -DNOF_ABLATE=1 build (timing experiments only)");
+    a.slot_mask = (uint32_t)slots - 1;
     {
         char *w = (char *)d->workspace;
-        if (!w) return nof::set_error(NOF_EINVAL, "field_step: workspace is NULL (nof_field_workspace_bytes)");
         const FieldWorkspace ws(d->R, d->S, d->mlp_dtype);
         a.feat = w + ws.feat;
         a.dfeat = w + ws.dfeat;
@@ -2831,21 +2824,11 @@ extern "C" int nof_field_step(const nof_field_desc *d, void *stream) {
         a.tile_gmask = (uint32_t *)(w + ws.gmask);
         a.rrec = (float *)(w + ws.rrec);
         a.ctile_list = (int *)(w + ws.ctile);
-        const int slots = d->scatter_slots ? d->scatter_slots : 512;
-        if (slots < 64 || slots > 2048 || (slots & (slots - 1)))
-            return nof::set_error(NOF_EINVAL, "field_step: scatter_slots must be a power of two in [64, 2048]");
-        a.slot_mask = (uint32_t)slots - 1;
     }
+
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        n_cu = 256;
-    if (d->mlp_dtype == NOF_F16 && d->table_dtype == NOF_F16)
-        return launch_field<_Float16, __half, 4>(a, n_cu, st);
-    if (d->mlp_dtype == NOF_F32 && d->table_dtype == NOF_F32)
-        return launch_field<float, float, 4>(a, n_cu, st);
-    return nof::set_error(NOF_EINVAL, "field_step: mlp/table dtype must both be f16 (amp) or both f32");
+    const int n_cu = cu_count();
+    return amp ? launch_field<_Float16, __half, 4>(a, n_cu, st) : launch_field<float, float, 4>(a, n_cu, st);
 }
 
 extern "C" int nof_field_timing(int32_t enable) {
@@ -2894,10 +2877,7 @@ extern "C" int nof_query_sdf(const void *table, int32_t table_dtype, const float
     a.bias = bias;
     nof::QueryArgs q{points, gx, gy, gz, nx, ny, nz, n, occ, occ_n, sdf};
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        n_cu = 256;
+    const int n_cu = cu_count();
     const int64_t ntile = (n + 31) / 32;
     const int blocks = (int)std::min<int64_t>((ntile + 3) / 4, (int64_t)n_cu * 2);
     if (mlp_dtype == NOF_F16) {

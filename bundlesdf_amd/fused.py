@@ -15,7 +15,9 @@ the nn.Parameters of the modules are views of it, so state_dict keys and
 shapes are the reference's (grid.py / nerf_helpers.py).
 """
 import ctypes
+import dataclasses
 import math
+import os
 
 import numpy as np
 import torch
@@ -107,9 +109,37 @@ class _HipOps:
                                                 1 if fs.amp else 0, _lib.stream_of(fs.scale)), "scaler")
 
 
+@dataclasses.dataclass(slots=True)
+class Knobs:
+    """Every tuning value a captured graph bakes in (FusedStep.knobs; _graph_key hashes them all).
+    slots: assigning an undeclared name raises AttributeError instead of leaving the default
+    configuration running under the wrong label."""
+    ablate: int = 0                    # timing-build ablation bits (scripts/ablate.py); must be 0 otherwise
+    scatter_slots: int = 0             # k_scatter LDS hash slots per wave; 0 -> 512
+    scatter_levels_per_wave: int = 0   # 0 = by batch size; tests force the per-ray or split scatter shape
+    bwd_flush: int = 0                 # amp MLP backward weight-gradient flush: 0 / 2 per block, 1 per wave
+    compact_per_block: int = 0         # 0 = by batch size; tests force the 16-flags-per-thread compaction (4096)
+    encode_group: int = 0              # k_encode levels in flight per lane: 0 = by batch size, or 1, 2, 4
+    quads_min_rays: int = 0            # 0 = the library's threshold (QUADS_MIN_RAYS); tests lower it
+    # the scatter's HBM-atomic counters (scatter_atomic_counts) outside debug steps and the kernel-timing
+    # pass, which always count; off in the timed path (they cost 9 us at 2048 rays)
+    count_atomics: bool = False
+    # XCD-contiguous block order for k_encode (bit 0; measured faster on sorted batches) and
+    # k_scatter (bit 1; measured slower): NOF_XCD_ORDER overrides for experiments
+    xcd_order: int = dataclasses.field(default_factory=lambda: int(os.environ.get("NOF_XCD_ORDER", "1")))
+    use_quads: bool = True             # amp: k_encode reads the xy-quad mirror on large batches
+    # the quad mirror rebuild runs on a side stream beside the prologue and trace; NOF_QUAD_FORK=0: in the step
+    quad_fork: bool = dataclasses.field(default_factory=lambda: os.environ.get("NOF_QUAD_FORK", "1") != "0")
+
+    # the knobs that are nof_field_desc fields of the same name (FusedStep._field_desc copies them)
+    DESCRIPTOR = ("ablate", "scatter_slots", "scatter_levels_per_wave", "bwd_flush", "compact_per_block",
+                  "encode_group", "quads_min_rays", "count_atomics", "xcd_order")
+
+
 class FusedStep:
     def __init__(self, cfg, pool, c2w, occ, grid, mlp, pose_array, amp=None, frame_start=None, blocks_per_cu=0,
                  process_group=None, world_size=1, time_kernels=False, feature_array=None, exchange=None):
+        # blocks_per_cu: accepted for callers that still pass it and ignored (the kernel whose grid it sized is gone)
         dev = pool.device
         if dev.type != "cuda":
             raise RuntimeError("FusedStep needs a HIP device (no CPU fallback)")
@@ -126,7 +156,7 @@ class FusedStep:
         self.L, self.C = grid.n_levels, grid.level_dim
         self.n_in = self.L * self.C
         assert self.C == 2 and self.n_in <= 32, "fused path: C=2, L<=16"
-        self.blocks_per_cu = blocks_per_cu
+        self.knobs = Knobs()
         self.frame_start = None
         if frame_start is not None:
             fst = np.asarray(frame_start, np.int64).ravel()
@@ -183,7 +213,6 @@ class FusedStep:
         self.quads = torch.empty(self.n_emb * 2, dtype=torch.int32, device=dev) if self.amp else None
         # its rebuild runs on this side stream, overlapping the prologue and trace (_fork_quad_mirror)
         self._side = torch.cuda.Stream(dev) if self.amp else None
-        self.quad_fork = __import__("os").environ.get("NOF_QUAD_FORK", "1") != "0"   # 0: rebuilt in the step
         if self.amp:
             _lib.check(_lib.lib().nof_to_half(_lib.ptr(self.P), _lib.ptr(self.emb16), self.n_emb,
                                               _lib.stream_of(self.P)), "to_half")
@@ -225,9 +254,6 @@ class FusedStep:
         self.pose_fg = torch.zeros(self.F, 12, dtype=torch.float32, device=dev)   # nof_pose_backward leaves it zero
         self.global_step = 0
         self.growth_interval = 2000        # GradScaler(growth_interval) of the reference (nerf_runner.py:159)
-        # XCD-contiguous block order for k_encode (bit 0; measured faster on sorted batches) and
-        # k_scatter (bit 1; measured slower): NOF_XCD_ORDER overrides for experiments
-        self.xcd_order = int(__import__("os").environ.get("NOF_XCD_ORDER", "1"))
         self._R = None
         # graph replay (graph_step): device step counter + the step block nof_step_schedule writes
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -411,7 +437,21 @@ class FusedStep:
             self.ex.wait_mirror()
 
     def _uses_quads(self):
-        return self.quads is not None and getattr(self, "use_quads", True)
+        return self.quads is not None and self.knobs.use_quads
+
+    def _field_desc(self, R):
+        """The nof_field_desc part nof_field_step and nof_quad_mirror share: batch size, table, level
+        table, quad mirror and every descriptor knob (Knobs.DESCRIPTOR)."""
+        D = _lib.FieldDesc()
+        D.R, D.L, D.C, D.D = R, self.L, self.C, 3
+        D.table = (self.emb16 if self.amp else self.P).data_ptr()
+        D.levels = self.levels.data_ptr()
+        D.table_dtype = D.mlp_dtype = _F16 if self.amp else _F32
+        if self._uses_quads():
+            D.table_quads, D.table_rows = self.quads.data_ptr(), self.n_emb // 2
+        for k in Knobs.DESCRIPTOR:
+            setattr(D, k, int(getattr(self.knobs, k)))
+        return D
 
     def _fork_quad_mirror(self, R):
         """Launch the encode's xy-quad mirror rebuild (nof_quad_mirror) on the side stream, forked from
@@ -419,20 +459,14 @@ class FusedStep:
         current stream waits for it) to call before the field pass, or None when the step rebuilds the
         mirror itself: no quads, the per-kernel timing pass (its encode bucket includes the rebuild), or
         the sharded exchange (the mirror all-gather lands only right before the field pass)."""
-        if (not self._uses_quads() or not self.quad_fork or self.time_kernels or R == 0
+        if (not self._uses_quads() or not self.knobs.quad_fork or self.time_kernels or R == 0
                 or (self.ex is not None and self.exchange == "sharded")):
             return None
         # below the library's quad threshold (nof_field_step: quads_min_rays, default 32,768 rays) the
         # encode reads the pair table and nof_quad_mirror does nothing: no fork / join nodes at all
-        if R < (int(getattr(self, "quads_min_rays", 0)) or QUADS_MIN_RAYS):
+        if R < (self.knobs.quads_min_rays or QUADS_MIN_RAYS):
             return None
-        D = _lib.FieldDesc()
-        D.R, D.L, D.C, D.D = R, self.L, self.C, 3
-        D.table, D.levels = self.emb16.data_ptr(), self.levels.data_ptr()
-        D.table_dtype = D.mlp_dtype = _F16
-        D.table_quads, D.table_rows = self.quads.data_ptr(), self.n_emb // 2
-        D.quads_min_rays = int(getattr(self, "quads_min_rays", 0))
-        D.ablate = getattr(self, "ablate", 0)
+        D = self._field_desc(R)
         main = torch.cuda.current_stream(self.dev)
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side):
@@ -473,7 +507,7 @@ class FusedStep:
             dbg = dict(z=torch.zeros(R, S, device=self.dev), raw=torch.zeros(R, S, 4, device=self.dev),
                        valid=torch.zeros(R, S, dtype=torch.uint8, device=self.dev),
                        rgb=torch.zeros(R, 3, device=self.dev))
-        D = _lib.FieldDesc()
+        D = self._field_desc(R)
         D.rays, D.tf, D.intervals, D.totals = self.rays.data_ptr(), self.tf_buf.data_ptr(), \
             self.intervals.data_ptr(), self.totals.data_ptr()
         if t_rand is not None:
@@ -481,7 +515,7 @@ class FusedStep:
             self._t_rand = t_rand
             D.t_rand = t_rand.data_ptr()
         D.seed = (self.global_step * 0x9E3779B1 + (0 if seed is None else seed)) & 0xFFFFFFFF
-        D.R, D.Kmax, D.N_oct, D.N_dep, D.S = R, self.Kmax, cfg["N_samples"], cfg["N_samples_around_depth"], S
+        D.Kmax, D.N_oct, D.N_dep, D.S = self.Kmax, cfg["N_samples"], cfg["N_samples_around_depth"], S
         D.perturb = 1 if perturb else 0
         D.near_sc, D.far_sc, D.trunc = cfg["near"] * sc, cfg["far"] * sc, trunc
         D.neg_trunc_ratio, D.sdf_lambda, D.fs_sdf = cfg["neg_trunc_ratio"], cfg["sdf_lambda"], cfg["fs_sdf"]
@@ -489,10 +523,6 @@ class FusedStep:
         D.empty_weight, D.trunc_weight = cfg["empty_weight"], cfg["trunc_weight"]
         D.fs_rgb_weight = float(cfg.get("fs_rgb_weight", 0) or 0)
         D.loss_scale = self.scale.data_ptr()
-        D.table = (self.emb16 if self.amp else self.P).data_ptr()
-        D.levels = self.levels.data_ptr()
-        D.L, D.C, D.D = self.L, self.C, 3
-        D.table_dtype = D.mlp_dtype = _F16 if self.amp else _F32
         D.frags, D.bias = self.frags.data_ptr(), self.bias.data_ptr()
         D.grad_table, D.grad_mlp = self.G.data_ptr(), self.G.data_ptr() + 4 * self.mlp_off
         D.grad_table16 = self.G16.data_ptr() if self.amp else None
@@ -500,28 +530,12 @@ class FusedStep:
         if dbg is not None:
             D.dbg_z, D.dbg_raw, D.dbg_valid, D.dbg_rgb = (dbg["z"].data_ptr(), dbg["raw"].data_ptr(),
                                                           dbg["valid"].data_ptr(), dbg["rgb"].data_ptr())
-        D.blocks_per_cu = self.blocks_per_cu
-        D.ablate = getattr(self, "ablate", 0)
         D.workspace = self.workspace.data_ptr()
-        D.scatter_slots = getattr(self, "scatter_slots", 0)
-        D.xcd_order = int(self.xcd_order)
         D.step_params = sp
         D.skip_pose_grad = 0 if self.pose_grad else 1
-        # 0 = by batch size; tests force the per-ray (large-batch) or split scatter shape
-        D.scatter_levels_per_wave = int(getattr(self, "scatter_levels_per_wave", 0))
-        D.bwd_flush = int(getattr(self, "bwd_flush", 0))
-        # table-gradient scatter: 0 / 2 the run-scan k_scatter (the only one left)
-        D.scatter_kernel = int(getattr(self, "scatter_kernel", 0))
-        # 0 = by batch size; tests force the 16-flags-per-thread compaction (4096) on small batches
-        D.compact_per_block = int(getattr(self, "compact_per_block", 0))
-        D.encode_group = int(getattr(self, "encode_group", 0))
-        # HBM-atomic counters of the scatter (scatter_atomic_counts): debug steps, the kernel-timing
-        # pass, or on request (count_atomics); off in the timed path (they cost 9 us at 2048 rays)
-        D.count_atomics = 1 if (debug or self.time_kernels or getattr(self, "count_atomics", False)) else 0
+        if debug or self.time_kernels:   # these always count the scatter's HBM atomics (Knobs.count_atomics)
+            D.count_atomics = 1
         if self._uses_quads():
-            D.table_quads, D.table_rows = self.quads.data_ptr(), self.n_emb // 2
-            # 0: the library's batch-size threshold; tests force the quad encode on small batches
-            D.quads_min_rays = int(getattr(self, "quads_min_rays", 0))
             D.quads_prebuilt = 0 if join_quads is None else 1
         D.n_ff = self.n_ff
         if self.n_ff:
@@ -648,15 +662,10 @@ class FusedStep:
 
     def _graph_key(self, *key):
         """Capture key: the call's own arguments plus every host value a captured graph
-        bakes in (kernel shape knobs, scaler interval, the loss / regulariser weights of
-        cfg) — change any of them and the next graph step captures again."""
-        knobs = (self.xcd_order, getattr(self, "scatter_levels_per_wave", 0), getattr(self, "scatter_slots", 0),
-                 getattr(self, "use_quads", True), getattr(self, "quads_min_rays", 0),
-                 getattr(self, "bwd_flush", 0), getattr(self, "compact_per_block", 0), getattr(self, "scatter_kernel", 0),
-                 getattr(self, "encode_group", 0), self.quad_fork,
-                 bool(getattr(self, "count_atomics", False)),
-                 getattr(self, "ablate", 0), self.blocks_per_cu, self.pose_grad, self.growth_interval)
-        return key + knobs + tuple(self.cfg.get(k) for k in self._CAPTURED_CFG)
+        bakes in (every knob, scaler interval, the loss / regulariser weights of cfg) —
+        change any of them and the next graph step captures again."""
+        return (key + dataclasses.astuple(self.knobs) + (self.pose_grad, self.growth_interval)
+                + tuple(self.cfg.get(k) for k in self._CAPTURED_CFG))
 
     # cfg entries the step reads on the host (descriptor scalars, regulariser weights, schedule)
     _CAPTURED_CFG = ("near", "far", "sc_factor", "N_samples", "N_samples_around_depth", "neg_trunc_ratio",
@@ -791,7 +800,7 @@ class FusedStep:
 
     def scatter_atomic_counts(self):
         """HBM atomics k_scatter issued in the last step: (table flush, probe overflow). Counted in
-        debug steps, the kernel-timing pass (time_kernels) and when count_atomics is set; zero
+        debug steps, the kernel-timing pass (time_kernels) and when knobs.count_atomics is set; zero
         otherwise."""
         return self.loss_acc[8:136].view(64, 2).sum(0)
 

@@ -176,8 +176,10 @@ int nof_pack_mlp(const float *mlp, const int32_t *idx, int32_t n_frag_elems, int
  * losses and the full backward. Accumulates (does not zero) grad_table and
  * grad_mlp; zeroes loss_acc [144] and then writes it; writes ray_grad [R,12] =
  * dL/d tf[frame][0:3,0:4] per ray. All gradients are multiplied by *loss_scale
- * (GradScaler). */
+ * (GradScaler). The struct has no padding (its 4-byte fields come in pairs between the
+ * pointers), so any field added or removed changes nof_field_desc_size(). */
 typedef struct {
+    /* ---- batch inputs and scalars */
     const float *rays;        /* [R,12] */
     const float *tf;          /* [F,16] */
     const float *intervals;   /* [R,Kmax,2] */
@@ -187,16 +189,29 @@ typedef struct {
     int32_t R, Kmax, N_oct, N_dep, S, perturb;
     float near_sc, far_sc, trunc, neg_trunc_ratio, sdf_lambda, fs_sdf, first_frame_weight;
     float rgb_weight, fs_weight, empty_weight, trunc_weight;
+    float fs_rgb_weight;      /* cfg fs_rgb_weight (train_loop :728-731): 0 = off; > 0 adds
+                                 fs_rgb_weight * mean(((sigmoid(rgb logits) - 1) * front)^2 * sample_weights),
+                                 the unweighted mean in loss_acc[140] */
+    int32_t skip_pose_grad;   /* 1: poses frozen (cfg optimize_poses = 0): no dL/dtf — the reference's grid
+                                 backward then skips dy_dx (inputs need no grad), so k_scatter skips the
+                                 corner re-gather and ray_grad is not written */
     const float *loss_scale;  /* device scalar */
+    const nof_step_params *step_params;   /* device, nullable: trunc and seed from the block (graph replay) */
+    /* ---- parameters */
     const void *table;        /* [T,2] table_dtype (the fp16 mirror under amp) */
     const float *levels;      /* [L,4] from nof_level_table: scale, res, row offset, rows (int bits) */
     uint32_t L, C, D;
     int32_t table_dtype, mlp_dtype;
+    int32_t n_ff;             /* cfg frame_features (0..3): FeatureArray channels fed to the colour net
+                                 (nerf_runner.py:221,234-235,1268-1277); 0 = none */
     const void *frags;        /* nof_pack_mlp output */
     const float *bias;
+    const float *ff;          /* [F, n_ff] f32 FeatureArray.data, or NULL */
+    /* ---- outputs */
     float *grad_table;        /* [T,2] f32 (fp32 mode) */
     void *grad_table16;       /* [T,2] f16 (amp mode: packed fp16x2 atomics, as the reference's __half2 path) */
     float *grad_mlp;          /* [9107 + 64*n_ff] f32 (mlp_layout.offsets) */
+    float *grad_ff;           /* [F, n_ff] f32 gradient (accumulated, scaled by *loss_scale), or NULL */
     float *ray_grad;          /* [R,12] f32 */
     float *loss_acc;          /* [144] f32: rgb, fs (free space), empty, sdf — normalised, unscaled;
                                  [4] samples inside the box, [5] samples through the backward, [6..7] not written
@@ -207,68 +222,43 @@ typedef struct {
                                  [136..139] executed tiles: sigma net, colour net, colour / sigma-only
                                  backward records; [140] fs_rgb loss (the reference's unweighted metric,
                                  train_loop :730; the loss adds fs_rgb_weight times it); [141..143] not written */
+    /* ---- debug outputs */
     float *dbg_z;             /* optional [R,S] */
     float *dbg_raw;           /* optional [R,S,4] (rgb logits, sdf) */
     uint8_t *dbg_valid;       /* optional [R,S] */
     float *dbg_rgb;           /* optional [R,3] */
-    int32_t blocks_per_cu;    /* reserved (the removed per-ray forward kernel's grid); ignored */
-    int32_t ablate;           /* timing-only ablation bits; must be 0 (results are wrong otherwise) */
-    void *workspace;          /* nof_field_workspace_bytes(R, S, mlp_dtype) bytes, caller-owned */
-    int32_t scatter_slots;    /* LDS hash slots per wave for the table-gradient scatter (0 -> 512; power of two, 64..2048) */
-    int32_t n_ff;             /* cfg frame_features (0..3): FeatureArray channels fed to the colour net
-                                 (nerf_runner.py:221,234-235,1268-1277); 0 = none */
-    const float *ff;          /* [F, n_ff] f32 FeatureArray.data, or NULL */
-    float *grad_ff;           /* [F, n_ff] f32 gradient (accumulated, scaled by *loss_scale), or NULL */
-    float fs_rgb_weight;      /* cfg fs_rgb_weight (train_loop :728-731): 0 = off; > 0 adds
-                                 fs_rgb_weight * mean(((sigmoid(rgb logits) - 1) * front)^2 * sample_weights),
-                                 the unweighted mean in loss_acc[140] */
-    int32_t xcd_order;        /* bit 0: k_encode, bit 1: k_scatter take their blocks in XCD-contiguous order
-                                 (each XCD's L2 serves a contiguous range of the batch); 0: dispatch order */
-    const nof_step_params *step_params;   /* device, nullable: trunc and seed from the block (graph replay) */
-    int32_t skip_pose_grad;   /* 1: poses frozen (cfg optimize_poses = 0): no dL/dtf — the reference's grid
-                                 backward then skips dy_dx (inputs need no grad), so k_scatter skips the
-                                 corner re-gather and ray_grad is not written */
-    int32_t scatter_levels_per_wave; /* 0: by batch size (a wave per ray from 192 K rays, 8 levels
-                                        per wave from 48 K, 4 from 8 K, else 2); n: scatter waves take
-                                        n levels of a ray */
+    /* ---- workspace: caller-owned scratch the step rewrites */
+    void *workspace;          /* nof_field_workspace_bytes(R, S, mlp_dtype) bytes */
     void *table_quads;        /* amp, optional (NULL: unused): 16 B per table row (n_rows = the last level's
                                  offset + size), rebuilt from `table` at the start of every field pass with
                                  R >= quads_min_rays; row r of a dense level holds the fp16 pairs of rows
                                  {r, r+1, r+rs, r+rs+1} (rs = res + 1), so k_encode reads a cell's 8
                                  corners in two 16-B loads (z, z+1) instead of four 8-B pair loads */
     int64_t table_rows;       /* rows of `table` (= table_quads' length in 16-B records) */
-    int32_t quads_min_rays;   /* batch size from which table_quads is used (0 -> 32768, the measured break-even
-                                 of its per-step rebuild); tests lower it to run the headline's quad encode on
-                                 oracle-sized batches */
-    int32_t scatter_kernel;   /* table-gradient scatter: 0 / 2 the run-scan k_scatter (lanes over samples, DPP
-                                 segmented scan; scatter_levels_per_wave). 1 (level-serial), 3 (hybrid) and 4
-                                 (paired run-scan) were measured slower and removed: NOF_EINVAL */
-    int32_t scatter_waves_per_ray; /* reserved (the removed level-serial scatter); ignored */
-    int32_t scatter_ls_levels; /* reserved (the removed hybrid scatter); ignored */
-    int32_t encode_sigma;     /* 0 / 1: the sigma net (layers 1-2) runs inside the encode kernel on the tile it
-                                 just encoded (sdf, sdf-loss terms, flags, colour-net input; features stored only
-                                 for backward tiles), the colour net runs tile-parallel over the colour tiles
-                                 (k_colour) and a thread per ray composites and finishes the losses
-                                 (k_ray_final). 2 and 3 (per-ray forward layouts) were removed: NOF_EINVAL */
-    int32_t bwd_flush;        /* amp MLP backward weight-gradient flush: 0 / 2 (default) summed over the 8-wave
-                                 block first (one atomic per element per block), 1 one atomic per element per wave */
+    int32_t quads_prebuilt;   /* 1: the caller rebuilt table_quads for this step with nof_quad_mirror (same
+                                 descriptor), ordered before this call (e.g. on a side stream joined by an
+                                 event, overlapping the prologue and trace); 0: nof_field_step rebuilds it */
+    /* ---- shape knobs: launch shapes and diagnostics, 0 = the library's choice */
     int32_t count_atomics;    /* 1: the scatter kernels count their HBM atomics (table flush, probe overflow) into
                                  loss_acc[8..135] (diagnostics); 0: those words stay zero */
-    int32_t scatter_flat;     /* reserved, must be 0 (the removed item-list scatter) */
+    int32_t ablate;           /* timing-only ablation bits; must be 0 (results are wrong otherwise) */
+    int32_t scatter_slots;   /* LDS hash slots per wave for the table-gradient scatter (0 -> 512; power of two, 64..2048) */
+    int32_t scatter_levels_per_wave; /* 0: by batch size (a wave per ray from 192 K rays, 8 levels
+                                        per wave from 48 K, 4 from 8 K, else 2); n: scatter waves take
+                                        n levels of a ray */
+    int32_t bwd_flush;        /* amp MLP backward weight-gradient flush: 0 / 2 (default) summed over the 8-wave
+                                 block first (one atomic per element per block), 1 one atomic per element per wave */
     int32_t compact_per_block; /* k_compact flags per block: 0 by batch size (4096 from 262,144 tiles, where each
                                   thread reads 16 flags with one 16-B load; else 512), or a multiple of 256 in
                                   [256, 4096] — the tests force 4096 on small batches to run the 16-flag path */
     int32_t encode_group;     /* k_encode levels whose corner gathers a lane keeps in flight together: 0 by batch
                                  size (1 from 8,192 rays, where 8 waves per SIMD hide the gathers; more below,
                                  where the grid is too small to), or 1, 2, 4 */
-    int32_t quads_prebuilt;   /* 1: the caller rebuilt table_quads for this step with nof_quad_mirror (same
-                                 descriptor), ordered before this call (e.g. on a side stream joined by an
-                                 event, overlapping the prologue and trace); 0: nof_field_step rebuilds it */
-    int32_t mlp_pass1_tiles;  /* reserved, 0 or 1 (one tile per wave): several tiles per wave iteration (k_mlp_bwd_s1)
-                                 were measured slower and removed — other values: NOF_EINVAL */
-    int32_t scatter_fuse_levels; /* reserved, 0 or 1: level-fused scatter chunks (a level's partial last chunk
-                                    continued with the next level's samples) were measured slower and removed */
-    int32_t encode_wpb;       /* reserved, 0 or 8: 16-wave encode blocks were measured slower and removed */
+    int32_t quads_min_rays;   /* batch size from which table_quads is used (0 -> 32768, the measured break-even
+                                 of its per-step rebuild); tests lower it to run the headline's quad encode on
+                                 oracle-sized batches */
+    int32_t xcd_order;        /* bit 0: k_encode, bit 1: k_scatter take their blocks in XCD-contiguous order
+                                 (each XCD's L2 serves a contiguous range of the batch); 0: dispatch order */
 } nof_field_desc;
 
 /* Launches on `stream`: k_ray_ctx (one 128-B context record per ray: direction,
@@ -284,6 +274,11 @@ typedef struct {
  * K = samples operands from LDS transposes), k_scatter (a wave per (ray, level
  * group): table-gradient scatter + input gradient). */
 int nof_field_step(const nof_field_desc *desc, void *stream);
+
+/* sizeof(nof_field_desc) of the build that made this library: a binder compares it with its own
+ * mirror of the struct right after loading, before any call that takes a descriptor (a library
+ * built from another header would read its pointers from the wrong offsets). */
+size_t nof_field_desc_size(void);
 
 /* The xy-quad mirror rebuild of nof_field_step (table -> table_quads), as its own launch: reads
  * table, levels, L, C, R, table_quads, table_rows, quads_min_rays and the dtypes of desc; a no-op

@@ -34,19 +34,16 @@ def main():
     cfg, pool, frame_start, c2w, occ, _, _ = bench.build_rank_scene(
         0, 1, frames, dict(amp=True, optimize_poses=int(os.environ.get("OPT_POSES", "1"))), dev)
     enc, net, pa = bench.make_models(cfg, frames, dev)
-    bpc = int(os.environ.get("BPC", "0"))
     fs = FusedStep(cfg, pool, torch.from_numpy(c2w), occ, enc, net, pa, amp=True,
-                   frame_start=frame_start, blocks_per_cu=bpc, time_kernels=True)
+                   frame_start=frame_start, time_kernels=True)
     if os.environ.get("USE_QUADS"):   # 0: the encode's pair loads instead of the xy-quad mirror
-        fs.use_quads = os.environ["USE_QUADS"] != "0"
+        fs.knobs.use_quads = os.environ["USE_QUADS"] != "0"
     if os.environ.get("LPW"):   # k_scatter levels per wave (0: the library's choice by batch size)
-        fs.scatter_levels_per_wave = int(os.environ["LPW"])
-    if os.environ.get("SK"):   # scatter kernel: 0 / 2 run-scan (other values: NOF_EINVAL)
-        fs.scatter_kernel = int(os.environ["SK"])
+        fs.knobs.scatter_levels_per_wave = int(os.environ["LPW"])
     if os.environ.get("BWDF"):   # MLP backward weight-gradient flush: 1 per wave, 2 block-reduced
-        fs.bwd_flush = int(os.environ["BWDF"])
+        fs.knobs.bwd_flush = int(os.environ["BWDF"])
     if "XCD" in os.environ:   # xcd_order bits (bit 0: k_encode, bit 1: k_scatter)
-        fs.xcd_order = int(os.environ["XCD"])
+        fs.knobs.xcd_order = int(os.environ["XCD"])
     for it in range(int(os.environ.get("WARM", "40"))):
         fs.step(ids=fs.sample_ids(2048, it))
     torch.cuda.synchronize()
@@ -63,8 +60,8 @@ def main():
         for name, m in MASKS.items():
             fs.wait_exchange()
             fs.P.copy_(P0); fs.M.copy_(M0); fs.V.copy_(V0); fs.emb16.copy_(E0)
-            fs.ablate = m
-            fs.scatter_slots = int(os.environ.get("SLOTS", "0"))
+            fs.knobs.ablate = m
+            fs.knobs.scatter_slots = int(os.environ.get("SLOTS", "0"))
             for it in range(3):
                 fs.step(ids=fs.sample_ids(2048, 100 + it))
             torch.cuda.synchronize()
@@ -83,7 +80,7 @@ def main():
             per[name].append(bd)
             res[name].append(sum(v for k, v in bd.items() if k.startswith("k_")))
     for name in MASKS:
-        print(json.dumps({"variant": name, "mask": MASKS[name], "bpc": bpc, "frames": frames, "lpw": os.environ.get("LPW", "0"), "sk": os.environ.get("SK", "0"), "bwdf": os.environ.get("BWDF", "0"), "quads": os.environ.get("USE_QUADS", "1"),
+        print(json.dumps({"variant": name, "mask": MASKS[name], "frames": frames, "lpw": os.environ.get("LPW", "0"), "bwdf": os.environ.get("BWDF", "0"), "quads": os.environ.get("USE_QUADS", "1"),
                           "optimize_poses": int(cfg["optimize_poses"]),
                           "lib": os.path.basename(os.environ.get("NOF_LIB", "libnof.so")), "slots": os.environ.get("SLOTS", "0"),
                           "field_ms_median": round(float(np.median([sum(v for k, v in b.items() if k.startswith("k_")) for b in per[name]])), 3),

@@ -1,6 +1,9 @@
 """Timing-build library of field_step.hip at a git revision (default HEAD) linked with the
 current timing-build objects of the other sources -> bundlesdf_amd/libnof_prev.so, for
 scripts/gpu_ab.sh A/B runs against libnof_ablate.so (PROD=1: production builds, against libnof.so).
+REV must not predate the nof_field_desc that dropped the deleted kernels' selector fields: an
+older field_step.hip names those fields and does not compile against the current include/nof.h
+(and a library built from the older header is refused at load: nof_field_desc_size).
 Usage: [PROD=1] python scripts/build_prev.py [REV]"""
 import glob
 import os

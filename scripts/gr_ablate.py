@@ -24,7 +24,7 @@ def main():
     fs = FusedStep(cfg, pool, torch.from_numpy(c2w), occ, enc, net, pa, amp=True, frame_start=frame_start,
                    feature_array=fa, time_kernels=True)
     if os.environ.get("LPW"):   # k_scatter levels per wave (0: the library's choice by batch size)
-        fs.scatter_levels_per_wave = int(os.environ["LPW"])
+        fs.knobs.scatter_levels_per_wave = int(os.environ["LPW"])
     for it in range(int(os.environ.get("WARM", "20"))):
         fs.step(ids=fs.sample_ids(rpf, it))
     torch.cuda.synchronize()
@@ -38,7 +38,7 @@ def main():
         for name, m in masks.items():
             fs.wait_exchange()
             fs.P.copy_(P0); fs.M.copy_(M0); fs.V.copy_(V0); fs.emb16.copy_(E0)
-            fs.ablate = m
+            fs.knobs.ablate = m
             for it in range(3):
                 fs.step(ids=fs.sample_ids(rpf, 100 + it))
             torch.cuda.synchronize()

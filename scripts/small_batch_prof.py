@@ -17,17 +17,15 @@ def main():
     enc, net, pa = bench.make_models(cfg, 64, dev)
     fs = FusedStep(cfg, pool, torch.from_numpy(c2w), occ, enc, net, pa, amp=True, frame_start=frame_start)
     if os.environ.get("ABLATE"):   # timing-build ablation bits (NOF_LIB = libnof_ablate.so)
-        fs.ablate = int(os.environ["ABLATE"])
+        fs.knobs.ablate = int(os.environ["ABLATE"])
     if os.environ.get("LPW"):   # k_scatter levels per wave (0: the library's choice by batch size)
-        fs.scatter_levels_per_wave = int(os.environ["LPW"])
-    if os.environ.get("SK"):   # scatter kernel: 0 / 2 run-scan (other values: NOF_EINVAL)
-        fs.scatter_kernel = int(os.environ["SK"])
+        fs.knobs.scatter_levels_per_wave = int(os.environ["LPW"])
     if os.environ.get("BWDF"):   # MLP backward weight-gradient flush: 1 per wave, 2 block-reduced (0: by batch size)
-        fs.bwd_flush = int(os.environ["BWDF"])
+        fs.knobs.bwd_flush = int(os.environ["BWDF"])
     if os.environ.get("SLOTS"):   # k_scatter LDS row-table slots per wave (0: the library's choice)
-        fs.scatter_slots = int(os.environ["SLOTS"])
+        fs.knobs.scatter_slots = int(os.environ["SLOTS"])
     if os.environ.get("EG"):   # k_encode levels in flight per lane (0: the library's choice by batch size)
-        fs.encode_group = int(os.environ["EG"])
+        fs.knobs.encode_group = int(os.environ["EG"])
     if os.environ.get("PER_FRAME") == "1":
         step = lambda: fs.graph_step(32)   # noqa: E731  64 frames x 32 rays = 2048 rays per step
     else:   # NerfRunner.train(): N_rand = 2048 ids of the epoch randperm over the pool (bench parity_mode)
@@ -48,7 +46,7 @@ def main():
     torch.cuda.synchronize()
     print(f"small batch: {t0.elapsed_time(t1) / n:.4f} ms/step (2048 rays, graph replay), "
           f"scatter levels per wave {os.environ.get('LPW', 'default')}, slots {os.environ.get('SLOTS', 'default')}, "
-          f"ablate {os.environ.get('ABLATE', '0')}, bwd_flush {os.environ.get('BWDF', 'default')}, scatter_kernel {os.environ.get('SK', 'default')}, "
+          f"ablate {os.environ.get('ABLATE', '0')}, bwd_flush {os.environ.get('BWDF', 'default')}, "
           f"encode_group {os.environ.get('EG', 'default')}")
 
 

@@ -82,7 +82,7 @@ def test_graph_recaptures_when_a_knob_changes(cuda_device):
     g0 = fs._graphs[1][0]
     fs.graph_step(256)
     assert fs._graphs[1][0] is g0                          # same knobs: replayed
-    fs.scatter_levels_per_wave = 4
+    fs.knobs.scatter_levels_per_wave = 4
     fs.graph_step(256)
     g1 = fs._graphs[1][0]
     assert g1 is not g0                                    # kernel shape knob: captured again

@@ -48,7 +48,7 @@ def headline(cuda_device):
 
 def _eager(fs, P0, ids, per):
     fs.reset_state(P0)
-    fs.compact_per_block = per
+    fs.knobs.compact_per_block = per
     out = fs.step(ids=ids, seed=11, debug=True)
     torch.cuda.synchronize()
     bl, cl = fs.tile_lists()
@@ -97,13 +97,13 @@ def test_headline_quad_mirror_fork_equals_inline(headline):
     the default) and inside the field pass (quads_prebuilt 0) give a bit-identical forward."""
     fs, P0, ids = headline
     try:
-        fs.quad_fork = False
+        fs.knobs.quad_fork = False
         a = _eager(fs, P0, ids, 0)
-        fs.quad_fork = True
+        fs.knobs.quad_fork = True
         fs.quads.fill_(-1)   # a stale or partial rebuild would show in the forward
         b = _eager(fs, P0, ids, 0)
     finally:
-        fs.quad_fork = True
+        fs.knobs.quad_fork = True
     assert np.isfinite(b["loss"][:8]).all()
     np.testing.assert_array_equal(a["raw"], b["raw"])
     np.testing.assert_array_equal(a["rgb"], b["rgb"])
@@ -122,7 +122,7 @@ def test_headline_step_subset_matches_oracle(headline):
     from oracle import nerf_step as NS
     fs, P0, ids = headline
     fs.reset_state(P0)
-    fs.compact_per_block = 0
+    fs.knobs.compact_per_block = 0
     cfg = fs.cfg
     R = ids.numel()
     S = cfg["N_samples"] + cfg["N_samples_around_depth"]
@@ -159,7 +159,7 @@ def test_headline_step_subset_matches_oracle(headline):
 
 def test_headline_graph_replay_equals_eager(headline):
     fs, P0, ids = headline
-    fs.compact_per_block = 0
+    fs.knobs.compact_per_block = 0
     fs.reset_state(P0)
     out = fs.step(ids=ids, seed=11)
     torch.cuda.synchronize()

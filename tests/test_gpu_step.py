@@ -183,7 +183,7 @@ AMP_SHAPES = dict(SHAPES, split2=dict(scatter_levels_per_wave=2))
 
 def _shape(fs, shape):
     for k, v in AMP_SHAPES[shape].items():
-        setattr(fs, k, v)
+        setattr(fs.knobs, k, v)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))
@@ -254,7 +254,7 @@ def test_fused_step_amp_matches_reference_amp_train_loop(golden_dir, cuda_device
     fs = FusedStep(cfg, torch.from_numpy(g["batch"]).to(dev), torch.from_numpy(g["c2w"]), torch.from_numpy(g["occ"]),
                    enc, net, pa, amp=True)
     for k, v in AMP_SHAPES_G4[shape].items():
-        setattr(fs, k, v)
+        setattr(fs.knobs, k, v)
     fs.scale.fill_(float(g["loss_scale"][0]))
     out = fs.step(ids=torch.arange(R, dtype=torch.int32, device=dev), t_rand=torch.from_numpy(g["t_rand"]), debug=True)
     torch.cuda.synchronize()
@@ -379,7 +379,7 @@ def test_amp_encode_quad_mirror_bit_identical(cuda_device):
         enc, net, pa = _build(dev, cfg, emb, mlp_w, pose, 16, 22, 128)
         fs = FusedStep(cfg, torch.from_numpy(batch).to(dev), torch.from_numpy(np.asarray(seq["poses"], np.float32)),
                        torch.from_numpy(occ), enc, net, pa, amp=True)
-        fs.use_quads = use
+        fs.knobs.use_quads = use
         fs.quads.zero_()
         out = fs.step(ids=torch.arange(R, dtype=torch.int32, device=dev), t_rand=torch.from_numpy(t_rand), debug=True)
         torch.cuda.synchronize()
@@ -593,19 +593,19 @@ def _oracle_ref(cfg, seq, batch, occ, t_rand, mlp_w, emb, pose, offs, enc, **kw)
 
 
 def _run_fused(cfg, seq, batch, occ, t_rand, mlp_w, emb, pose, dev, amp=False, global_step=0, slots=0, L=16, log2T=22,
-               finest=128, scale=None, shape=None, knobs=None, blocks_per_cu=0):
+               finest=128, scale=None, shape=None, knobs=None):
     from bundlesdf_amd.fused import FusedStep
     enc, net, pa = _build(dev, cfg, emb, mlp_w, pose, L, log2T, finest)
     R = batch.shape[0]
     fs = FusedStep(cfg, torch.from_numpy(batch).to(dev), torch.from_numpy(np.asarray(seq["poses"], np.float32)),
-                   torch.from_numpy(occ), enc, net, pa, amp=amp, blocks_per_cu=blocks_per_cu)
+                   torch.from_numpy(occ), enc, net, pa, amp=amp)
     for k, v in (knobs or {}).items():
-        setattr(fs, k, v)
+        setattr(fs.knobs, k, v)
     if fs.quads is not None:
         fs.quads.zero_()          # a non-zero quad table afterwards proves the quad encode ran
     fs.global_step = global_step
     if slots:
-        fs.scatter_slots = slots
+        fs.knobs.scatter_slots = slots
     if scale is not None:
         fs.scale.fill_(scale)
     if shape is not None:
@@ -629,13 +629,13 @@ def test_scatter_probe_overflow_path_matches_oracle(cuda_device):
     _METRICS["overflow/n_direct_atomics"] = n_overflow
 
 
-def _amp_vs_oracle(prefix, dev, shape=None, knobs=None, blocks_per_cu=0, seed=3, R=384):
+def _amp_vs_oracle(prefix, dev, shape=None, knobs=None, seed=3, R=384):
     cfg, seq, batch, occ, t_rand, mlp_w, emb, pose, offs = _scene_case(seed=seed, R=R)
     cfg["amp"] = True
     # loss scale 1024: at the GradScaler's initial 2^16 the reference's fp16 weight gradients of this
     # case overflow (the step would be skipped; test_gpu_optim covers that path)
     fs, enc, out = _run_fused(cfg, seq, batch, occ, t_rand, mlp_w, emb, pose, dev, amp=True, scale=1024.0,
-                              shape=shape, knobs=knobs, blocks_per_cu=blocks_per_cu)
+                              shape=shape, knobs=knobs)
     ref = aligned_ref(prefix, out["dbg"], lambda **kw: _oracle_ref(cfg, seq, batch, occ, t_rand, mlp_w, emb, pose, offs,
                                                                     enc, amp=True, loss_scale=1024.0, **kw),
                       batch, cfg, NS.truncation(cfg))
