@@ -42,6 +42,8 @@ _SIGNATURES = {
     "nof_field_step": ([_p, _p], _int),
     "nof_field_desc_size": ([], ctypes.c_size_t),
     "nof_quad_mirror": ([_p, _p], _int),
+    "nof_render_workspace_bytes": ([_i32, _i32], ctypes.c_size_t),
+    "nof_render_rays": ([_p, _p, _p], _int),
     "nof_field_workspace_bytes": ([_i32, _i32, _i32], ctypes.c_size_t),
     "nof_field_workspace_offsets": ([_i32, _i32, _i32, _p, _i32], _int),
     "nof_field_timing": ([_i32], _int),
@@ -95,6 +97,11 @@ class FieldDesc(ctypes.Structure):
                 # shape knobs
                 ("count_atomics", _i32), ("ablate", _i32), ("scatter_slots", _i32), ("scatter_levels_per_wave", _i32), ("bwd_flush", _i32),
                 ("compact_per_block", _i32), ("encode_group", _i32), ("quads_min_rays", _i32), ("xcd_order", _i32)]
+
+
+class RenderOut(ctypes.Structure):
+    """Mirror of nof_render_out (include/nof.h): the outputs of nof_render_rays."""
+    _fields_ = [("rgb", _p), ("depth", _p), ("z", _p), ("sdf", _p), ("valid", _p), ("workspace", _p)]
 
 
 class StepParams(ctypes.Structure):

@@ -1132,6 +1132,18 @@ __device__ __forceinline__ RayCtx build_ray(const FieldArgs &a, int r) {
     for (int i = 0; i < 3; ++i) c.ff[i] = i < a.n_ff ? a.ff[(size_t)c.frame * a.n_ff + i] : 0.f;
     return c;
 }
+// ray r's record (load_ray reads it back)
+__device__ __forceinline__ void store_ray_ctx(float *rctx, int r, const RayCtx &c) {
+    float4 *o = reinterpret_cast<float4 *>(rctx + (size_t)r * RCTX);
+    o[0] = make_float4(c.dir[0], c.dir[1], c.dir[2], c.tgt[0]);
+    o[1] = make_float4(c.tgt[1], c.tgt[2], c.Rm[0][0], c.Rm[0][1]);
+    o[2] = make_float4(c.Rm[0][2], c.Rm[1][0], c.Rm[1][1], c.Rm[1][2]);
+    o[3] = make_float4(c.Rm[2][0], c.Rm[2][1], c.Rm[2][2], c.tv[0]);
+    o[4] = make_float4(c.tv[1], c.tv[2], c.vd[0], c.vd[1]);
+    o[5] = make_float4(c.vd[2], c.depth, c.total, __int_as_float(c.frame));
+    o[6] = make_float4(__int_as_float(c.rtype), c.ff[0], c.ff[1], c.ff[2]);
+    o[7] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
 __global__ __launch_bounds__(256) void k_ray_ctx(FieldArgs a_) {
     const FieldArgs a = step_args(a_);
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1141,15 +1153,7 @@ __global__ __launch_bounds__(256) void k_ray_ctx(FieldArgs a_) {
     for (int i = r; i < LOSS_ACC_WORDS; i += gridDim.x * blockDim.x) a.loss_acc[i] = 0.f;
     if (r >= a.R) return;
     const RayCtx c = build_ray(a, r);
-    float4 *o = reinterpret_cast<float4 *>(a.rctx + (size_t)r * RCTX);
-    o[0] = make_float4(c.dir[0], c.dir[1], c.dir[2], c.tgt[0]);
-    o[1] = make_float4(c.tgt[1], c.tgt[2], c.Rm[0][0], c.Rm[0][1]);
-    o[2] = make_float4(c.Rm[0][2], c.Rm[1][0], c.Rm[1][1], c.Rm[1][2]);
-    o[3] = make_float4(c.Rm[2][0], c.Rm[2][1], c.Rm[2][2], c.tv[0]);
-    o[4] = make_float4(c.tv[1], c.tv[2], c.vd[0], c.vd[1]);
-    o[5] = make_float4(c.vd[2], c.depth, c.total, __int_as_float(c.frame));
-    o[6] = make_float4(__int_as_float(c.rtype), c.ff[0], c.ff[1], c.ff[2]);
-    o[7] = make_float4(0.f, 0.f, 0.f, 0.f);
+    store_ray_ctx(a.rctx, r, c);
 }
 // every caller passes a wave-uniform ray: the record is read through the constant address
 // space (scalar loads, the context stays in scalar registers)
@@ -2295,6 +2299,8 @@ __global__ __launch_bounds__(256) void k_query_sdf(FieldArgs a, QueryArgs q) {
     }
 }
 
+#include "field_render.h"   // the forward-only ray render (k_render_ctx, k_render, k_render_final)
+
 // end of the field pass: loss_acc[LOSS_FOLD_DST[k]] += sum of the LOSS_COPIES copies of slot k
 __device__ __forceinline__ void loss_fold(const float *__restrict__ part, float *__restrict__ loss_acc, int k) {
     if (k >= LOSS_FOLD_N) return;
@@ -2888,4 +2894,79 @@ extern "C" int nof_query_sdf(const void *table, int32_t table_dtype, const float
         hipLaunchKernelGGL((nof::k_query_sdf<float, float>), dim3(blocks), dim3(256), lds, st, a, q);
     }
     return nof::check_launch("query_sdf");
+}
+
+namespace {
+// the render's workspace: per-ray context records, then the per-tile records
+struct RenderWorkspace {
+    size_t rctx, rrec, total;
+    RenderWorkspace(int R, int S) {
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        size_t o = 0;
+        rctx = o; o += al((size_t)R * nof::RCTX * 4);
+        rrec = o; o += al((size_t)R * (S / 32) * nof::RREC * 4);
+        total = o;
+    }
+};
+}  // namespace
+
+extern "C" size_t nof_render_workspace_bytes(int32_t R, int32_t S) {
+    return (R < 0 || S <= 0) ? 0 : RenderWorkspace(R, S).total;
+}
+
+extern "C" int nof_render_rays(const nof_field_desc *d, const nof_render_out *o, void *stream) {
+    // every refusal comes before the first HIP call, as in nof_field_step
+    if (!d || !o) return nof::set_error(NOF_EINVAL, "render_rays: desc / out is NULL");
+    if (d->S <= 0 || d->S % 32 != 0 || d->S > 320 || d->N_oct + d->N_dep != d->S)
+        return nof::set_error(NOF_EINVAL, "render_rays: S=%d must be N_oct+N_dep, a multiple of 32, <= 320", d->S);
+    if (d->L == 0 || d->L > 16 || d->C != 2 || d->D != 3)
+        return nof::set_error(NOF_EINVAL, "render_rays: needs D=3, C=2, 1<=L<=16 (got %u,%u,%u)", d->D, d->C, d->L);
+    if (!o->rgb) return nof::set_error(NOF_EINVAL, "render_rays: out.rgb is NULL");
+    if (!o->depth) return nof::set_error(NOF_EINVAL, "render_rays: out.depth is NULL");
+    if (d->R < 0 || (int64_t)d->R * (d->S / 32) > INT32_MAX)
+        return nof::set_error(NOF_EINVAL, "render_rays: R=%d (0 <= R, R * S / 32 < 2^31)", d->R);
+    if (d->R == 0) return NOF_OK;
+    if (d->Kmax <= 0) return nof::set_error(NOF_EINVAL, "render_rays: Kmax=%d", d->Kmax);
+    if (!d->rays || !d->tf || !d->intervals || !d->totals)
+        return nof::set_error(NOF_EINVAL, "render_rays: rays / tf / intervals / totals is NULL (nof_trace_rays)");
+    if (!d->table || !d->levels || !d->frags || !d->bias)
+        return nof::set_error(NOF_EINVAL, "render_rays: table / levels / frags / bias is NULL");
+    if (d->n_ff < 0 || d->n_ff > 3 || (d->n_ff > 0 && !d->ff))
+        return nof::set_error(NOF_EINVAL, "render_rays: frame_features must be 0..3 with ff set (got %d)", d->n_ff);
+    const bool amp = d->mlp_dtype == NOF_F16 && d->table_dtype == NOF_F16;
+    if (!amp && !(d->mlp_dtype == NOF_F32 && d->table_dtype == NOF_F32))
+        return nof::set_error(NOF_EINVAL, "render_rays: mlp/table dtype must both be f16 (amp) or both f32");
+    if (!o->workspace) return nof::set_error(NOF_EINVAL, "render_rays: out.workspace is NULL (nof_render_workspace_bytes)");
+
+    nof::FieldArgs a{};
+    a.rays = d->rays; a.tf = d->tf; a.intervals = d->intervals; a.totals = d->totals;
+    a.R = d->R; a.Kmax = d->Kmax; a.N_oct = d->N_oct; a.N_dep = d->N_dep; a.S = d->S;
+    a.perturb = 0;   // render_images renders with perturb=False: no draws are read
+    a.near_sc = d->near_sc; a.far_sc = d->far_sc; a.trunc = d->trunc;
+    a.ntr = d->neg_trunc_ratio; a.lambda = d->sdf_lambda;
+    a.table = d->table; a.levels = (const float4 *)d->levels; a.L = d->L; a.mlp_in = (int)(d->L * d->C);
+    a.n_ff = d->n_ff; a.ff = d->ff; a.frags = d->frags; a.bias = d->bias;
+    const RenderWorkspace ws(d->R, d->S);
+    char *w = (char *)o->workspace;
+    a.rctx = (float *)(w + ws.rctx);
+    const nof::RenderOut ro{o->rgb, o->depth, o->z, o->sdf, o->valid, (float *)(w + ws.rrec)};
+
+    hipStream_t st = (hipStream_t)stream;
+    const int n_cu = cu_count();
+    hipLaunchKernelGGL(nof::k_render_ctx, dim3(nof::div_up(a.R, 256)), dim3(256), 0, st, a);
+    int rc = nof::check_launch("render_rays(ctx)");
+    if (rc) return rc;
+    const int64_t n_tiles = (int64_t)a.R * (a.S / 32);
+    // persistent 8-wave blocks: at most 4 per CU (the staged fragments: 30 KB fp16, 54 KB fp32)
+    const dim3 grid((uint32_t)std::min<int64_t>((n_tiles + nof::RENDER_WPB - 1) / nof::RENDER_WPB, (int64_t)n_cu * 4));
+    if (amp)
+        hipLaunchKernelGGL((nof::k_render<_Float16, __half>), grid, dim3(nof::RENDER_WPB * 64),
+                           nof::render_lds_bytes<_Float16>(), st, a, ro);
+    else
+        hipLaunchKernelGGL((nof::k_render<float, float>), grid, dim3(nof::RENDER_WPB * 64),
+                           nof::render_lds_bytes<float>(), st, a, ro);
+    rc = nof::check_launch("render_rays(render)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(nof::k_render_final, dim3(nof::div_up(a.R, 256)), dim3(256), 0, st, a, ro);
+    return nof::check_launch("render_rays(final)");
 }

@@ -840,6 +840,82 @@ class FusedStep:
             0 if occ_t is None else int(occ_t.shape[0]), _lib.ptr(sdf), _lib.stream_of(sdf)), "query_sdf")
         return sdf
 
+    def _render_buffers(self, n):
+        """The render's own trace outputs and workspace for chunks of up to n rays (kept between
+        calls, grown on demand): the training step's buffers, ids and captured graphs are not
+        touched."""
+        rb = getattr(self, "_render_buf", None)
+        if rb is None or rb["n"] < n:
+            d = self.dev
+            S = self.cfg["N_samples"] + self.cfg["N_samples_around_depth"]
+            rb = dict(n=n, rays=torch.empty(n, 12, device=d), intervals=torch.empty(n, self.Kmax, 2, device=d),
+                      totals=torch.empty(n, device=d),
+                      workspace=torch.empty(int(_lib.lib().nof_render_workspace_bytes(n, S)), dtype=torch.uint8,
+                                            device=d))
+            self._render_buf = rb
+        return rb
+
+    @torch.no_grad()
+    def render_rays(self, ids, global_step=None, samples=False, chunk=32768):
+        """Forward-only render of pool[ids] through the current field (nof_render_rays: what
+        render_images, nerf_runner.py:584-634, takes from render() with perturb=False): returns
+        {"rgb" [R,3], "depth" [R]} as float32 device tensors in ids order — the depth-guided
+        colour composite of raw2outputs and the zero-crossing depth of :602-610 (far * sc_factor
+        on rays without a sign change) — and, with samples=True, {"z", "sdf" [R,S] float32,
+        "valid" [R,S] bool}. trunc is truncation(cfg, global_step), global_step defaulting to the
+        trainer's. The rays go through in chunks of at most `chunk` (the trace's interval buffer
+        is chunk x Kmax x 2 floats); the result does not depend on chunk. No parameter, gradient,
+        optimiser, scaler or step state is written and captured graphs stay valid; the prologue
+        re-derives tf / the MLP fragments from the current parameters, as every step does."""
+        cfg = self.cfg
+        ids = torch.as_tensor(ids).to(self.dev).to(torch.int32).contiguous().view(-1)
+        R = int(ids.numel())
+        S = cfg["N_samples"] + cfg["N_samples_around_depth"]
+        dev = self.dev
+        out = {"rgb": torch.empty(R, 3, device=dev), "depth": torch.empty(R, device=dev)}
+        if samples:
+            out.update(z=torch.empty(R, S, device=dev), sdf=torch.empty(R, S, device=dev),
+                       valid=torch.empty(R, S, dtype=torch.uint8, device=dev))
+        if R > 0:
+            chunk = max(1, int(chunk))
+            L = _lib.lib()
+            st = _lib.stream_of(self.P)
+            self.wait_exchange()
+            self._prologue()
+            sc = cfg["sc_factor"]
+            trunc = truncation(cfg, self.global_step if global_step is None else global_step)
+            rb = self._render_buffers(min(chunk, R))
+            for lo in range(0, R, chunk):
+                n = min(chunk, R - lo)
+                _lib.check(L.nof_trace_rays(_lib.ptr(self.pool), _lib.ctypes.c_void_p(ids.data_ptr() + 4 * lo), n,
+                                            _lib.ptr(self.tf_buf), _lib.ptr(self.occ), self.Nocc, self.Kmax,
+                                            cfg["near"] * sc, cfg["far"] * sc, trunc, _lib.ptr(rb["rays"]),
+                                            _lib.ptr(rb["intervals"]), _lib.ptr(rb["totals"]), None, None, st),
+                           "trace_rays")
+                D = _lib.FieldDesc()
+                D.R, D.L, D.C, D.D = n, self.L, self.C, 3
+                D.table = (self.emb16 if self.amp else self.P).data_ptr()   # the pair table, never the quad mirror
+                D.levels = self.levels.data_ptr()
+                D.table_dtype = D.mlp_dtype = _F16 if self.amp else _F32
+                D.rays, D.tf, D.intervals, D.totals = (rb["rays"].data_ptr(), self.tf_buf.data_ptr(),
+                                                       rb["intervals"].data_ptr(), rb["totals"].data_ptr())
+                D.Kmax, D.N_oct, D.N_dep, D.S = self.Kmax, cfg["N_samples"], cfg["N_samples_around_depth"], S
+                D.near_sc, D.far_sc, D.trunc = cfg["near"] * sc, cfg["far"] * sc, trunc
+                D.neg_trunc_ratio, D.sdf_lambda = cfg["neg_trunc_ratio"], cfg["sdf_lambda"]
+                D.frags, D.bias = self.frags.data_ptr(), self.bias.data_ptr()
+                D.n_ff = self.n_ff
+                if self.n_ff:
+                    D.ff = self.P.data_ptr() + 4 * self.feat_off
+                O = _lib.RenderOut(rgb=out["rgb"].data_ptr() + 12 * lo, depth=out["depth"].data_ptr() + 4 * lo,
+                                   workspace=rb["workspace"].data_ptr())
+                if samples:
+                    O.z, O.sdf = out["z"].data_ptr() + 4 * S * lo, out["sdf"].data_ptr() + 4 * S * lo
+                    O.valid = out["valid"].data_ptr() + S * lo
+                _lib.check(L.nof_render_rays(_lib.ctypes.byref(D), _lib.ctypes.byref(O), st), "render_rays")
+        if samples:
+            out["valid"] = out["valid"].bool()
+        return out
+
     def refresh_half_table(self):
         """Re-derive the fp16 table mirror after the fp32 table was written from outside (load_weights,
         reset_state). Under the sharded exchange the rank's mirror shard is re-copied as well: the

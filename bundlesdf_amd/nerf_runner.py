@@ -28,8 +28,17 @@ eikonal_weight > 0). fs_rgb_weight and the trunc_decay_type schedules run on
 the device.
 extract_mesh runs the fused SDF query kernel + device marching cubes
 (bundlesdf_amd/mesh.py); mesh_texture_from_train_images bakes on the device
-(bundlesdf_amd/texture.py)."""
+(bundlesdf_amd/texture.py).
+render_images (:584-634) renders one frame's pool rays through the current field
+with the forward-only render kernel (FusedStep.render_rays -> nof_render_rays: no
+backward, no optimiser, no state written) and places them in full-size images.
+train() runs train_loop's periodic outputs (:764-851) after each step: the
+checkpoint (i_weights), the validation canvas image_step_%07d.png (i_img), the
+metric log (i_print), the two meshes (i_mesh) and the optimised poses (i_pose),
+each every cfg[key] steps; a missing key, 999999 or more, or np.inf mean never,
+and then train() is exactly the bare step loop (no sync, graph replay kept)."""
 import logging
+import os
 import random
 
 import numpy as np
@@ -207,6 +216,38 @@ def _check_supported(cfg):
         raise NotImplementedError("fused MI355X path: mode 'sdf' only")
 
 
+HOOK_KEYS = ("i_weights", "i_img", "i_print", "i_mesh", "i_pose")   # train_loop's order (:764-851)
+HOOK_NEVER = 999999   # the configs' "never" (config.yml; run_custom.py:135 sets np.inf instead)
+
+
+def hook_periods(cfg):
+    """The periodic outputs of train_loop (:764-851) this config switches on: {key: period}.
+    A missing key, a period of 999999 or more, np.inf (or anything not a positive finite
+    number) mean never."""
+    out = {}
+    for k in HOOK_KEYS:
+        v = cfg.get(k)
+        if v is None or isinstance(v, bool) or not np.isfinite(v) or v <= 0 or v >= HOOK_NEVER:
+            continue
+        out[k] = int(v)
+    return out
+
+
+def hooks_due(periods, g):
+    """Keys of `periods` (hook_periods) that fire after the step that ran as global step g: the
+    reference's g % period == 0 and g > 0; i_print has no g > 0 condition (:793)."""
+    return [k for k, v in periods.items() if g % v == 0 and (g > 0 or k == "i_print")]
+
+
+def validation_frames(ids):
+    """train_loop :768-773: of the sorted frame ids, every max(1, n // 5)-th plus the last."""
+    ids = sorted(int(i) for i in ids)
+    out = ids[::max(1, len(ids) // 5)]
+    if ids[-1] not in out:
+        out.append(ids[-1])
+    return out
+
+
 class NerfRunner:
     def __init__(self, cfg, images, depths, masks, normal_maps, poses, K, _run=None, occ_masks=None,
                  build_octree_pcd=None, device=None):
@@ -377,6 +418,7 @@ class NerfRunner:
         """nerf_runner.py:854-862: N_iters = n_step + 1 fused steps on DataLoader batches."""
         set_seed(0)
         out = None
+        periods = hook_periods(self.cfg)   # empty with every i_* key at its default: the bare loop
         for it in range(self.N_iters):
             if self.N_iters >= 10 and it % (self.N_iters // 10) == 0:
                 logging.info(f"train progress {it}/{self.N_iters}")
@@ -388,8 +430,144 @@ class NerfRunner:
             else:
                 perm, k = self.data_loader.next_slice()
                 out = self.trainer.graph_step_epoch(perm, k, self.data_loader.batch_size)
+            if periods:   # host integers only: checking adds no device work and no sync
+                for key in hooks_due(periods, self.global_step):
+                    getattr(self, "_hook_" + key[2:])(out)   # i_img -> _hook_img
             self.global_step += 1
         return out
+
+    # ------------------------------------------------------------ train_loop's periodic outputs (:764-851)
+    # Each runs after the step that ran as self.global_step (not yet incremented; the trainer's own
+    # counter is one ahead) and may synchronise.
+    def _save_path(self, name):
+        d = self.cfg["save_dir"]
+        os.makedirs(d, exist_ok=True)
+        return os.path.join(d, name)
+
+    def _artifact(self, path):
+        if self._run is not None:
+            self._run.add_artifact(path)
+
+    def _hook_weights(self, out=None):
+        self.save_weights(out_file=self._save_path("model_latest.pth"), models=self.models)
+
+    def validation_canvas(self):
+        """train_loop :768-786: one row per validation frame (validation_frames of the pool's frame
+        ids) — rendered | ground-truth colour, rendered | ground-truth depth over far, and the ray mask
+        over the dimmed render — stacked: uint8 [rows * H, 5 * W, 3]."""
+        ids = validation_frames(torch.unique(self.rays[:, 8]).cpu().numpy().astype(int).tolist())
+        far = self.cfg["far"] * self.cfg["sc_factor"]
+        canvas = []
+        for frame_idx in ids:
+            rgb, depth, ray_mask, gt_rgb, gt_depth, _ = self.render_images(frame_idx)
+            mask_vis = np.clip((rgb * 255 * 0.2 + ray_mask * 0.8).astype(np.uint8), 0, 255)
+            rgb = np.concatenate((rgb, gt_rgb), axis=1)
+            gt_depth = np.clip(gt_depth, self.cfg["near"] * self.cfg["sc_factor"], far)
+            depth_vis = np.concatenate((to8b(depth / far), to8b(gt_depth / far)), axis=1)
+            depth_vis = np.tile(depth_vis[..., None], (1, 1, 3))
+            canvas.append(np.concatenate((to8b(rgb), depth_vis, mask_vis), axis=1))
+        return np.concatenate(canvas, axis=0).astype(np.uint8)
+
+    def _hook_img(self, out=None):
+        from .mesh import write_png
+        path = self._save_path(f"image_step_{self.global_step:07d}.png")
+        write_png(path, self.validation_canvas())
+        self._artifact(path)
+
+    def _hook_print(self, out):
+        """:793-821 with the loss terms the fused step keeps (loss_terms: rgb, free-space, empty, sdf,
+        -, -, reg_features, pose_reg, all weighted; fs_rgb_loss unweighted), under the reference's
+        metric names where it has one (its fs_loss is free-space + empty)."""
+        lt = [float(v) for v in out["loss_terms"].tolist()]
+        fs_rgb = float(out["fs_rgb_loss"])
+        metrics = {"loss": sum(lt[:4]) + lt[6] + lt[7] + float(self.cfg.get("fs_rgb_weight", 0) or 0) * fs_rgb,
+                   "rgb_loss": lt[0], "fs_rgb_loss": fs_rgb, "fs_loss": lt[1] + lt[2], "empty_loss": lt[2],
+                   "sdf_loss": lt[3], "truncation(meter)": self.get_truncation() / self.cfg["sc_factor"]}
+        if self.cfg["optimize_poses"]:
+            metrics["pose_reg"] = lt[7]
+        if self.models.get("feature_array") is not None:
+            metrics["reg_features"] = lt[6]
+        logging.info(f"Iter: {self.global_step}, valid_samples: {int(lt[4])}, "
+                     + "".join(f"{k}: {v:.7f}, " for k, v in metrics.items()))
+        if self._run is not None:
+            for k, v in metrics.items():
+                self._run.log_scalar(k, v, self.global_step)
+
+    def _pose_array_or_none(self):
+        return self.models["pose_array"] if self.cfg["optimize_poses"] else None
+
+    def _hook_mesh(self, out=None):
+        from .handoff import get_optimized_poses_in_real_world
+        from .mesh import mesh_to_real_world
+        mesh = self.extract_mesh(isolevel=0, voxel_size=self.cfg["mesh_resolution"])
+        self.mesh = None if mesh is None else mesh.copy()
+        if mesh is None:
+            return
+        path = self._save_path(f"step_{self.global_step:07d}_mesh_normalized_space.obj")
+        mesh.export(path)
+        self._artifact(path)
+        path = self._save_path(f"step_{self.global_step:07d}_mesh_real_world.obj")
+        offset = np.eye(4)
+        if self._pose_array_or_none() is not None:
+            _, offset = get_optimized_poses_in_real_world(self.poses, self.models["pose_array"],
+                                                          translation=self.cfg["translation"],
+                                                          sc_factor=self.cfg["sc_factor"])
+        mesh = mesh_to_real_world(mesh, offset, translation=self.cfg["translation"], sc_factor=self.cfg["sc_factor"])
+        mesh.export(path)
+        self._artifact(path)
+
+    def _hook_pose(self, out=None):
+        from .handoff import get_optimized_poses_in_real_world
+        poses = self.poses
+        if self._pose_array_or_none() is not None:
+            poses, _ = get_optimized_poses_in_real_world(self.poses, self.models["pose_array"],
+                                                         translation=self.cfg["translation"],
+                                                         sc_factor=self.cfg["sc_factor"])
+        path = self._save_path(f"step_{self.global_step:07d}_optimized_poses.txt")
+        np.savetxt(path, np.asarray(poses).reshape(-1, 4))
+        self._artifact(path)
+
+    @torch.no_grad()
+    def render_images(self, img_i, cur_rays=None):
+        """nerf_runner.py:584-634: frame img_i's pool rays rendered through the current field
+        (perturb=False) and placed at their pixels. Returns (rgb_full [H,W,3] f64, depth_full [H,W]
+        f64, ray_mask_full [H,W,3] u8: type-0 rays red, type-1 green, gt_rgb_full, gt_depth_full,
+        extras) with the reference's shapes, dtypes and pixel placement (flip y and z of the ray
+        direction, project with self.K, round). The frame's rays are selected on the device from the
+        resident pool and rendered by FusedStep.render_rays (forward only); only the rays' rgb, depth,
+        directions, type and ground-truth columns come to the host. A frame with no rays gives zero images.
+        extras = {"z_vals", "sdf", "valid_samples"} ([n,S] device tensors): unlike the reference's
+        it holds no 'raw' colour logits per sample (the render composites them in registers) — the
+        reference's only caller (train_loop :776) discards extras.
+        cur_rays is not supported: the reference's own path for it reads an undefined frame_ids
+        (:593, NameError)."""
+        if cur_rays is not None:
+            raise NotImplementedError("render_images(cur_rays=...): the reference reads an undefined frame_ids "
+                                      "there (nerf_runner.py:593); pass img_i only")
+        ids = torch.nonzero(self.rays[:, 8] == img_i).view(-1)
+        r = self.trainer.render_rays(ids, global_step=self.global_step, samples=True)
+        rays = self.rays[ids][:, [0, 1, 2, 3, 4, 5, 6, 9]].cpu().numpy()
+        rgb, depth = r["rgb"].cpu().numpy(), r["depth"].cpu().numpy()
+        extras = {"z_vals": r["z"], "sdf": r["sdf"], "valid_samples": r["valid"]}
+        rgb_full = np.zeros((self.H, self.W, 3), dtype=float)
+        depth_full = np.zeros((self.H, self.W), dtype=float)
+        ray_mask_full = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        gt_rgb_full = np.zeros((self.H, self.W, 3), dtype=float)
+        gt_depth_full = np.zeros((self.H, self.W), dtype=float)
+        if len(rays):
+            X = rays[:, :3].copy()
+            X[:, [1, 2]] = -X[:, [1, 2]]
+            projected = (self.K @ X.T).T
+            uvs = (projected / projected[:, 2].reshape(-1, 1)).round().astype(int)
+            ray_type = rays[:, 7]
+            good, unc = uvs[ray_type == 0], uvs[ray_type == 1]
+            ray_mask_full[good[:, 1], good[:, 0]] = [255, 0, 0]
+            ray_mask_full[unc[:, 1], unc[:, 0]] = [0, 255, 0]
+            rgb_full[uvs[:, 1], uvs[:, 0]] = rgb.reshape(-1, 3)
+            depth_full[uvs[:, 1], uvs[:, 0]] = depth.reshape(-1)
+            gt_rgb_full[uvs[:, 1], uvs[:, 0]] = rays[:, 3:6]
+            gt_depth_full[uvs[:, 1], uvs[:, 0]] = rays[:, 6]
+        return rgb_full, depth_full, ray_mask_full, gt_rgb_full, gt_depth_full, extras
 
     def get_truncation(self):
         """nerf_runner.py:661-674: the truncation band of the current step (linear / exp

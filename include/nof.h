@@ -287,6 +287,38 @@ size_t nof_field_desc_size(void);
  * mirror is this library's layout for the encode's corner gathers (gridencoder.cu:145-205). */
 int nof_quad_mirror(const nof_field_desc *desc, void *stream);
 
+/* Forward-only ray render (replaces what NerfRunner.render_images, nerf_runner.py:584-634, takes
+ * from render() with perturb=False: render_rays :1043-1087, raw2outputs :1131-1168 and the depth
+ * rule of :602-610). Outputs of nof_render_rays; z / sdf / valid are optional (NULL: nothing per
+ * sample is written to memory). */
+typedef struct {
+    float *rgb;        /* [R,3] depth-guided composite of the sigmoid colours: sum over valid samples of
+                          w sigmoid(rgb logits) / (sum over all samples of w + 1e-10), w the bell weight of
+                          raw2outputs (0 for rays with depth > far) */
+    float *depth;      /* [R] signs[i] = sdf[i+1] * sdf[i] (float32) over the ray's S samples in the
+                          reference's order (N_oct octree samples, then N_dep around-depth samples, unsorted):
+                          far_sc when every signs[i] > 0, else z[j], j the first i with signs[i] < 0 (j = 0
+                          when there is none) — computed from the z / sdf values this call returns */
+    float *z;          /* optional [R,S] sample z */
+    float *sdf;        /* optional [R,S] sigma-net output; samples outside [-1,1]^3 carry the net's output on
+                          a zero encoding (run_network :1246,1265) */
+    uint8_t *valid;    /* optional [R,S] 1 = inside [-1,1]^3 */
+    void *workspace;   /* nof_render_workspace_bytes(R, S) bytes of scratch (per-ray context records,
+                          one 48-B record per 32-sample tile) */
+} nof_render_out;
+
+size_t nof_render_workspace_bytes(int32_t R, int32_t S);
+
+/* Reads of desc: rays, tf, intervals, totals (nof_trace_rays output), R, Kmax, N_oct, N_dep, S,
+ * near_sc, far_sc, trunc, neg_trunc_ratio, sdf_lambda, table, levels, L, C, D, the dtypes, n_ff, ff,
+ * frags, bias. Everything else is ignored: sampling is unperturbed (no t_rand, no seed), the pair
+ * table is read (never table_quads), no gradient, loss or workspace field is touched. Launches
+ * k_render_ctx (a thread per ray), k_render (a wave per 32-sample tile: sampling, encode, sigma net,
+ * colour net where a valid sample has weight) and k_render_final (a thread per ray sums its tiles in
+ * order and applies the depth rule): no atomics, so two calls on the same inputs are bit-identical.
+ * The descriptor is validated before the first HIP call; R == 0 returns NOF_OK with no launch. */
+int nof_render_rays(const nof_field_desc *desc, const nof_render_out *out, void *stream);
+
 /* SDF query (replaces run_network_density, nerf_runner.py:1306-1346, as used
  * by extract_mesh :1349-1382): clip to [-1,1], multires encode, sigma net.
  * Point mode: points [n,3] f32. Grid mode (points NULL): the nx*ny*nz points
