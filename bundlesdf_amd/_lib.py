@@ -51,6 +51,7 @@ _SIGNATURES = {
     "nof_step_prologue": ([_p, _p, _p, _p, _p, _i32, _f32, _f32, _p, _p, _p, _p, _i32, _i32, _p, _p, _int, _p], _int),
     "nof_query_sdf": ([_p, _i32, _p, ctypes.c_uint32, _p, _p, _i32, _i32, _p, ctypes.c_int64, _p, _p, _p, _i32, _i32,
                        _i32, _p, _i32, _p, _p], _int),
+    "nof_query_field": ([_p, _i32, _p, _u32, _p, _p, _i32, _i32, _p, _i64, _p, _i32, _i32, _i32, _p, _p, _p, _p], _int),
     "nof_pose_backward": ([_p, _p, _i32, _p, _i32, _p, _p, _p], _int),
     "nof_field_timing_collect": ([_p, _i32, _p], _int),
     "nof_level_table": ([_u32, _f32, _u32, _p, _p], None),

@@ -2299,6 +2299,7 @@ __global__ __launch_bounds__(256) void k_query_sdf(FieldArgs a, QueryArgs q) {
     }
 }
 
+#include "field_query.h"    // the point query with gradient and colour (k_query_field)
 #include "field_render.h"   // the forward-only ray render (k_render_ctx, k_render, k_render_final)
 
 // end of the field pass: loss_acc[LOSS_FOLD_DST[k]] += sum of the LOSS_COPIES copies of slot k
@@ -2894,6 +2895,55 @@ extern "C" int nof_query_sdf(const void *table, int32_t table_dtype, const float
         hipLaunchKernelGGL((nof::k_query_sdf<float, float>), dim3(blocks), dim3(256), lds, st, a, q);
     }
     return nof::check_launch("query_sdf");
+}
+
+extern "C" int nof_query_field(const void *table, int32_t table_dtype, const float *level_table, uint32_t L,
+                               const void *frags, const float *bias, int32_t mlp_dtype, int32_t mlp_in,
+                               const float *points, int64_t n, const float *ff, int32_t n_frames, int32_t n_ff,
+                               int32_t frame_id, float *sdf, float *grad, float *rgb, void *stream) {
+    // every refusal comes before the first HIP call
+    if (!sdf && !grad && !rgb) return nof::set_error(NOF_EINVAL, "query_field: no output requested (sdf, grad and rgb are NULL)");
+    if (n < 0) return nof::set_error(NOF_EINVAL, "query_field: n=%lld is negative", (long long)n);
+    if (!points && n > 0) return nof::set_error(NOF_EINVAL, "query_field: points is NULL with n=%lld", (long long)n);
+    if (table_dtype != mlp_dtype || (mlp_dtype != NOF_F16 && mlp_dtype != NOF_F32))
+        return nof::set_error(NOF_EINVAL, "query_field: table and MLP dtypes must match (both f16 or both f32)");
+    if (L == 0 || L > 16 || mlp_in != (int)L * 2)
+        return nof::set_error(NOF_EINVAL, "query_field: needs 1<=L<=16 and C=2 (got L=%u, mlp_in=%d)", L, mlp_in);
+    if (!table || !level_table || !frags || !bias)
+        return nof::set_error(NOF_EINVAL, "query_field: table / level_table / frags / bias is NULL");
+    if (n_ff < 0 || n_ff > 3 || (n_ff > 0 && !ff))
+        return nof::set_error(NOF_EINVAL, "query_field: frame_features must be 0..3 with ff set (got %d)", n_ff);
+    if (ff && n_ff > 0 && (frame_id < 0 || frame_id >= n_frames))
+        return nof::set_error(NOF_EINVAL, "query_field: frame_id %d outside the %d frames", frame_id, n_frames);
+    if (n == 0) return NOF_OK;
+    nof::FieldArgs a{};
+    a.table = table;
+    a.levels = reinterpret_cast<const float4 *>(level_table);
+    a.L = L;
+    a.mlp_in = mlp_in;
+    a.frags = frags;
+    a.bias = bias;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_cu = cu_count();
+    const int64_t ntile = (n + 31) / 32;
+    const int blocks = (int)std::min<int64_t>((ntile + 3) / 4, (int64_t)n_cu * 2);
+    const size_t lds_sdf = (size_t)nof::N_FRAGS * 64 * 8 * (mlp_dtype == NOF_F16 ? 2 : 4) + 5 * 64 * 4;
+    const size_t lds = lds_sdf + (mlp_dtype == NOF_F16 ? 5 * 64 * 4 : 0);   // amp: + the fp16-rounded bias image
+    if (!grad && !rgb) {   // the SDF alone is k_query_sdf's work: its kernel runs it
+        nof::QueryArgs q{points, nullptr, nullptr, nullptr, 0, 0, 0, n, nullptr, 0, sdf};
+        if (mlp_dtype == NOF_F16)
+            hipLaunchKernelGGL((nof::k_query_sdf<_Float16, __half>), dim3(blocks), dim3(256), lds_sdf, st, a, q);
+        else
+            hipLaunchKernelGGL((nof::k_query_sdf<float, float>), dim3(blocks), dim3(256), lds_sdf, st, a, q);
+        return nof::check_launch("query_field(sdf)");
+    }
+    const bool with_ff = ff && n_ff > 0;
+    nof::QueryFieldArgs q{points, n, with_ff ? ff + (size_t)frame_id * n_ff : nullptr, with_ff ? n_ff : 0, sdf, grad, rgb};
+    if (mlp_dtype == NOF_F16)
+        hipLaunchKernelGGL((nof::k_query_field<_Float16, __half>), dim3(blocks), dim3(256), lds, st, a, q);
+    else
+        hipLaunchKernelGGL((nof::k_query_field<float, float>), dim3(blocks), dim3(256), lds, st, a, q);
+    return nof::check_launch("query_field");
 }
 
 namespace {

@@ -840,6 +840,46 @@ class FusedStep:
             0 if occ_t is None else int(occ_t.shape[0]), _lib.ptr(sdf), _lib.stream_of(sdf)), "query_sdf")
         return sdf
 
+    @torch.no_grad()
+    def query_field(self, points, sdf=True, normals=False, colour=False, frame_id=0, chunk=1 << 22):
+        """The current field at points [n,3] (nof_query_field): a dict of float32 device tensors with
+        the requested keys — "sdf" [n] (bit-identical to query_sdf(points=...)), "normals" [n,3] (the
+        analytic d sdf / d point of run_network_density(get_normals=True), nerf_runner.py:1306-1346:
+        not normalised, taken at the clipped point) and "colour" [n,3] (sigmoid of the colour net at
+        view direction 0 with frame `frame_id`'s features, as mesh_vertex_color_from_network queries
+        it, :1411-1428; a point outside [-1,1]^3 is not clipped there but reads a zero embedding).
+        The points go through in launches of at most `chunk`; the result does not depend on chunk.
+        No training buffer is written and captured graphs stay valid."""
+        if not (sdf or normals or colour):
+            raise ValueError("query_field: request at least one of sdf, normals, colour")
+        self.wait_exchange()
+        self.pack_mlp()
+        dev = self.dev
+        pts = torch.as_tensor(points, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        out = {}
+        if sdf:
+            out["sdf"] = torch.empty(n, dtype=torch.float32, device=dev)
+        if normals:
+            out["normals"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        if colour:
+            out["colour"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        dt = _F16 if self.amp else _F32
+        vp = _lib.ctypes.c_void_p
+        ff = vp(self.P.data_ptr() + 4 * self.feat_off) if self.n_ff else None
+        chunk = max(1, int(chunk))
+        for lo in range(0, n, chunk):
+            m = min(chunk, n - lo)
+
+            def at(key, width):
+                return vp(out[key].data_ptr() + 4 * width * lo) if key in out else None
+            _lib.check(_lib.lib().nof_query_field(
+                _lib.ptr(self.emb16 if self.amp else self.P), dt, _lib.ptr(self.levels), self.L, _lib.ptr(self.frags),
+                _lib.ptr(self.bias), dt, self.n_in, vp(pts.data_ptr() + 12 * lo), m, ff, self.F if self.n_ff else 0,
+                self.n_ff, int(frame_id), at("sdf", 1), at("normals", 3), at("colour", 3), _lib.stream_of(pts)),
+                "query_field")
+        return out
+
     def _render_buffers(self, n):
         """The render's own trace outputs and workspace for chunks of up to n rays (kept between
         calls, grown on demand): the training step's buffers, ids and captured graphs are not

@@ -105,6 +105,8 @@ class Mesh:
         self.faces = np.asarray(faces, np.int64)
         self.uv = None          # [V,2] texture coordinates (texture.unwrap)
         self.texture = None     # [H,W,3] uint8 image (texture.bake_texture), row 0 = top
+        self.vertex_normals = None   # [V,3] float, unit length (NerfRunner.mesh_vertex_normals_from_network)
+        self.vertex_colors = None    # [V,3] uint8 (NerfRunner.mesh_vertex_color_from_network)
 
     @property
     def face_normals(self):
@@ -115,6 +117,8 @@ class Mesh:
     def apply_transform(self, T):
         T = np.asarray(T, np.float64)
         self.vertices = self.vertices @ T[:3, :3].T + T[:3, 3]
+        if self.vertex_normals is not None:   # directions: the rotation part only
+            self.vertex_normals = np.asarray(self.vertex_normals, np.float64) @ T[:3, :3].T
         return self
 
     @property
@@ -125,12 +129,22 @@ class Mesh:
         m = Mesh(self.vertices.copy(), self.faces.copy())
         m.uv = None if self.uv is None else self.uv.copy()
         m.texture = None if self.texture is None else self.texture.copy()
+        m.vertex_normals = None if self.vertex_normals is None else self.vertex_normals.copy()
+        m.vertex_colors = None if self.vertex_colors is None else self.vertex_colors.copy()
         return m
+
+    def _take_vertex_rows(self, rows):
+        """Per-vertex attributes follow their vertices (rows: index array or mask of the old vertices)."""
+        if self.vertex_normals is not None:
+            self.vertex_normals = np.asarray(self.vertex_normals)[rows]
+        if self.vertex_colors is not None:
+            self.vertex_colors = np.asarray(self.vertex_colors)[rows]
 
     def merge_vertices(self):
         """Weld vertices at identical positions (marching_cubes output already shares them)."""
-        v, inv = np.unique(self.vertices, axis=0, return_inverse=True)
+        v, first, inv = np.unique(self.vertices, axis=0, return_index=True, return_inverse=True)
         self.vertices, self.faces = v, inv.reshape(-1)[self.faces]
+        self._take_vertex_rows(first)   # a welded vertex keeps the attributes of its first occurrence
         return self
 
     def remove_duplicate_faces(self):
@@ -147,6 +161,7 @@ class Mesh:
         keep = mask[self.faces].all(1)
         self.faces = remap[self.faces[keep]]
         self.vertices = self.vertices[mask]
+        self._take_vertex_rows(mask)
         return self
 
     def export(self, path):
@@ -157,13 +172,27 @@ class Mesh:
             with open(path, "w") as f:
                 if textured:
                     f.write(f"mtllib {os.path.basename(base)}.mtl\nusemtl material0\n")
-                for v in self.vertices:
-                    f.write(f"v {v[0]:.6f} {v[1]:.6f} {v[2]:.6f}\n")
+                if self.vertex_colors is not None:   # the common "v x y z r g b" extension, colours in [0, 1]
+                    for v, c in zip(self.vertices, np.asarray(self.vertex_colors, np.float64) / 255.0):
+                        f.write(f"v {v[0]:.6f} {v[1]:.6f} {v[2]:.6f} {c[0]:.6f} {c[1]:.6f} {c[2]:.6f}\n")
+                else:
+                    for v in self.vertices:
+                        f.write(f"v {v[0]:.6f} {v[1]:.6f} {v[2]:.6f}\n")
+                normals = self.vertex_normals is not None
+                if normals:
+                    for v in self.vertex_normals:
+                        f.write(f"vn {v[0]:.6f} {v[1]:.6f} {v[2]:.6f}\n")
                 if textured:
                     for t in self.uv:
                         f.write(f"vt {t[0]:.6f} {t[1]:.6f}\n")
                     for t in self.faces + 1:
-                        f.write(f"f {t[0]}/{t[0]} {t[1]}/{t[1]} {t[2]}/{t[2]}\n")
+                        if normals:
+                            f.write(f"f {t[0]}/{t[0]}/{t[0]} {t[1]}/{t[1]}/{t[1]} {t[2]}/{t[2]}/{t[2]}\n")
+                        else:
+                            f.write(f"f {t[0]}/{t[0]} {t[1]}/{t[1]} {t[2]}/{t[2]}\n")
+                elif normals:
+                    for t in self.faces + 1:
+                        f.write(f"f {t[0]}//{t[0]} {t[1]}//{t[1]} {t[2]}//{t[2]}\n")
                 else:
                     for t in self.faces + 1:
                         f.write(f"f {t[0]} {t[1]} {t[2]}\n")
@@ -173,11 +202,24 @@ class Mesh:
                 write_png(base + ".png", self.texture)
         elif path.endswith(".ply"):
             with open(path, "wb") as f:
+                props, fields = "", [("p", "<f4", 3)]
+                if self.vertex_normals is not None:
+                    props += "property float nx\nproperty float ny\nproperty float nz\n"
+                    fields.append(("n", "<f4", 3))
+                if self.vertex_colors is not None:
+                    props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                    fields.append(("c", "u1", 3))
                 f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(self.vertices)}\n"
-                         "property float x\nproperty float y\nproperty float z\n"
+                         "property float x\nproperty float y\nproperty float z\n" + props +
                          f"element face {len(self.faces)}\nproperty list uchar int vertex_indices\n"
                          "end_header\n").encode())
-                f.write(self.vertices.astype("<f4").tobytes())
+                vrec = np.zeros(len(self.vertices), dtype=fields)
+                vrec["p"] = self.vertices
+                if self.vertex_normals is not None:
+                    vrec["n"] = self.vertex_normals
+                if self.vertex_colors is not None:
+                    vrec["c"] = self.vertex_colors
+                f.write(vrec.tobytes())
                 rec = np.zeros(len(self.faces), dtype=[("n", "u1"), ("i", "<i4", 3)])
                 rec["n"] = 3
                 rec["i"] = self.faces

@@ -503,6 +503,10 @@ class NerfRunner:
         self.mesh = None if mesh is None else mesh.copy()
         if mesh is None:
             return
+        if self.cfg.get("mesh_vertex_attributes"):   # not a reference key: off unless asked for
+            self.mesh_vertex_normals_from_network(mesh)
+            self.mesh_vertex_color_from_network(mesh)
+            self.mesh = mesh.copy()
         path = self._save_path(f"step_{self.global_step:07d}_mesh_normalized_space.obj")
         mesh.export(path)
         self._artifact(path)
@@ -605,13 +609,38 @@ class NerfRunner:
 
     def run_network_density(self, inputs, get_normals=False):
         """nerf_runner.py:1306-1346: sdf of points already in normalised space ([-1,1]
-        clip), as [N,1] plus the all-true valid mask (hash-grid embedder)."""
-        if get_normals:
-            raise NotImplementedError("run_network_density(get_normals=True) is not implemented on the fused path")
+        clip), as [N,1] plus the all-true valid mask (hash-grid embedder). With get_normals the
+        outputs are [..., 4] = torch.cat((sdf, d sdf / d point), -1) as the reference lays them
+        out: the analytic gradient of the fused field (FusedStep.query_field) at the clipped point,
+        not normalised."""
         flat = torch.as_tensor(inputs, dtype=torch.float32).reshape(-1, 3)
+        if get_normals:
+            r = self.trainer.query_field(flat, sdf=True, normals=True)
+            sdf = r["sdf"]
+            valid = torch.ones(flat.shape[0], dtype=torch.bool, device=sdf.device)
+            return torch.cat((sdf[:, None], r["normals"]), -1).reshape(*inputs.shape[:-1], 4), valid
         sdf = self.trainer.query_sdf(points=flat)
         valid = torch.ones(flat.shape[0], dtype=torch.bool, device=sdf.device)
         return sdf.reshape(*inputs.shape[:-1], 1), valid
+
+    def mesh_vertex_color_from_network(self, mesh):
+        """nerf_runner.py:1411-1428: the colour net at every vertex (normalised space) with view
+        direction 0, identity transform and frame 0's features; sets mesh.vertex_colors (uint8 [V,3],
+        (colors * 255) truncated as the reference casts it) and returns the mesh."""
+        rgb = self.trainer.query_field(np.asarray(mesh.vertices, np.float32), sdf=False, colour=True, frame_id=0)
+        mesh.vertex_colors = (rgb["colour"].cpu().numpy() * 255).astype(np.uint8)
+        return mesh
+
+    def mesh_vertex_normals_from_network(self, mesh):
+        """Sets mesh.vertex_normals (float [V,3]) to the unit-length SDF gradient of the field at every
+        vertex (normalised space); a zero gradient stays zero. Returns the mesh. No reference
+        counterpart: the reference drops skimage's marching-cubes normals and leaves vertex normals to
+        trimesh; here they come from the network, as run_network_density(get_normals=True) gives them."""
+        g = self.trainer.query_field(np.asarray(mesh.vertices, np.float32), sdf=False, normals=True)
+        g = g["normals"].cpu().numpy().astype(np.float64)
+        norm = np.linalg.norm(g, axis=1, keepdims=True)
+        mesh.vertex_normals = np.where(norm > 0, g / np.where(norm > 0, norm, 1.0), 0.0)
+        return mesh
 
     @torch.no_grad()
     def extract_mesh(self, level=None, voxel_size=0.003, isolevel=0.0, return_sigma=False):

@@ -331,6 +331,27 @@ int nof_query_sdf(const void *table, int32_t table_dtype, const float *level_tab
                   const float *gx, const float *gy, const float *gz, int32_t nx, int32_t ny, int32_t nz,
                   const uint8_t *occ, int32_t occ_n, float *sdf, void *stream);
 
+/* Field point query: SDF, its gradient with respect to the point, and colour at points [n,3] f32
+ * (run_network_density(get_normals=True), nerf_runner.py:1306-1346, and run_network as
+ * mesh_vertex_color_from_network calls it, :1411-1428). table / table_dtype / level_table / L / frags /
+ * bias / mlp_dtype / mlp_in as for nof_query_sdf (the gradient reads the backward fragments FR_B2 /
+ * FR_B1 that nof_pack_mlp already packs). Outputs, each nullable, at least one set:
+ *   sdf  [n]   f32: bit-identical to nof_query_sdf on the same points (clip to [-1,1]);
+ *   grad [n,3] f32: d sdf / d point at the CLIPPED point (the reference's autograd leaf is the clipped
+ *                   tensor: a point outside the box gets the gradient at its clipped position); amp
+ *                   rounds where the reference's autograd rounds (fp16 dy_dx, fp16 Linear backward
+ *                   results, fp16 input-backward sums in level order);
+ *   rgb  [n,3] f32: sigmoid of the colour net at view direction (0,0,0) with the frame features of
+ *                   frame_id (ff [n_frames, n_ff] f32, NULL / n_ff 0 for a model without). Validity is
+ *                   run_network's: a point with any |x| > 1 is NOT clipped, its grid embedding is zero
+ *                   (:1244-1265) — unlike sdf / grad of the same call.
+ * Every argument is validated before the first HIP call; n == 0 returns NOF_OK with no launch. No
+ * atomics, nothing written but the outputs. With sdf alone the launch is nof_query_sdf's kernel. */
+int nof_query_field(const void *table, int32_t table_dtype, const float *level_table, uint32_t L, const void *frags,
+                    const float *bias, int32_t mlp_dtype, int32_t mlp_in, const float *points, int64_t n,
+                    const float *ff, int32_t n_frames, int32_t n_ff, int32_t frame_id, float *sdf, float *grad,
+                    float *rgb, void *stream);
+
 /* Pose corrections on the device (replaces PoseArray.get_matrices,
  * nerf_helpers.py:127-154, and tf = T @ c2w, nerf_runner.py:1050-1052, with
  * their autograd). data [F,6] f32 (PoseArray.data); c2w [F,4,4] f32;
