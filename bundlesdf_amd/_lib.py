@@ -44,6 +44,8 @@ _SIGNATURES = {
     "nof_quad_mirror": ([_p, _p], _int),
     "nof_render_workspace_bytes": ([_i32, _i32], ctypes.c_size_t),
     "nof_render_rays": ([_p, _p, _p], _int),
+    "nof_render_view_workspace_bytes": ([_i32, _i32], ctypes.c_size_t),
+    "nof_render_view": ([_p, _p, _p, _p], _int),
     "nof_field_workspace_bytes": ([_i32, _i32, _i32], ctypes.c_size_t),
     "nof_field_workspace_offsets": ([_i32, _i32, _i32, _p, _i32], _int),
     "nof_field_timing": ([_i32], _int),
@@ -103,6 +105,19 @@ class FieldDesc(ctypes.Structure):
 class RenderOut(ctypes.Structure):
     """Mirror of nof_render_out (include/nof.h): the outputs of nof_render_rays."""
     _fields_ = [("rgb", _p), ("depth", _p), ("z", _p), ("sdf", _p), ("valid", _p), ("workspace", _p)]
+
+
+class ViewDesc(ctypes.Structure):
+    """Mirror of nof_view_desc (include/nof.h): the camera and march settings of nof_render_view."""
+    _fields_ = [("c2w", _f32 * 16), ("K", _f32 * 9), ("H", _i32), ("W", _i32), ("pixels", _p), ("n", _i32),
+                ("pixel0", _i32), ("step", _f32), ("max_steps", _i32), ("n_refine", _i32), ("frame_id", _i32),
+                ("n_frames", _i32), ("occ_n", _i32), ("occ", _p)]
+
+
+class ViewOut(ctypes.Structure):
+    """Mirror of nof_view_out (include/nof.h): the outputs of nof_render_view."""
+    _fields_ = [("t", _p), ("depth", _p), ("normal", _p), ("rgb", _p), ("hit", _p), ("index", _p), ("tiles", _p),
+                ("workspace", _p)]
 
 
 class StepParams(ctypes.Structure):

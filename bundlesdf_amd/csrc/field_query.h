@@ -101,9 +101,145 @@ __device__ __forceinline__ void encode_level_dx(const FieldArgs &a, const LevelI
     }
 }
 
+// One tile of 32 points (lane n and n + 32 hold point n): the forward, the gradient and the colour pass
+// described above, as k_query_field runs them; the surface render's shading kernel (field_view.h) runs
+// the same tile at its hit points. x: the point as given (not clipped); sdf is returned on every lane,
+// r (d sdf / d x01 summed over the levels: the gradient is 0.5 r) and logit on the lanes of half 0.
+// VIEW: the colour net's SH input is sh3(vdir) as sh_frag lays it out, else sh3(0) (the constant term).
+template <typename TM, typename TT, bool VIEW>
+__device__ __forceinline__ void query_tile(const FieldArgs &a, const LdsW<TM> &W, const float *s_b, const float *s_bc,
+                                           float x[3], bool inb, bool want_sdf, bool want_dx, bool want_rgb,
+                                           const float *ff, int n_ff, const float vdir[3], int lane, float &sdf,
+                                           float r[3], float logit[3]) {
+    typedef typename FragT<TM>::T Frag;
+    constexpr bool HALF = sizeof(TM) == 2;
+    const int h = lane >> 5;
+    // run_network's validity (:1244); the SDF and the gradient take the clipped point instead
+    const bool inside = fabsf(x[0]) <= 1.f && fabsf(x[1]) <= 1.f && fabsf(x[2]) <= 1.f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) x[d] = fminf(fmaxf(x[d], -1.f), 1.f);   // torch.clip(inputs, -1, 1)
+    const float x01[3] = {(x[0] + 1) / 2, (x[1] + 1) / 2, (x[2] + 1) / 2};
+    // colour alone: the zero embedding of a point outside the box needs no gather
+    const bool enc = inb && (want_sdf || inside);
+    Acts<TM> A;
+    Frag Xc[2];            // amp: the colour pass's features (half-kernel rounding)
+    float dydx[8][3][2];   // this lane's 8 levels (k = 4 ss + qq)
+#pragma unroll
+    for (int ss = 0; ss < 2; ++ss) {
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            const int lv = lane_level(ss, qq, h), k = 4 * ss + qq;
+            float v[2] = {0.f, 0.f}, vh[2] = {0.f, 0.f};
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { dydx[k][d][0] = 0.f; dydx[k][d][1] = 0.f; }
+            if (enc && lv < (int)a.L)
+                encode_level_dx<TT>(a, level_info(a, lv), x01, v, want_dx, dydx[k], want_rgb && inside, vh);
+            frag_set<TM>(A.X[ss], 2 * qq, v[0]);
+            frag_set<TM>(A.X[ss], 2 * qq + 1, v[1]);
+            if constexpr (HALF) {
+                frag_set<TM>(Xc[ss], 2 * qq, vh[0]);
+                frag_set<TM>(Xc[ss], 2 * qq + 1, vh[1]);
+            }
+        }
+    }
+    sdf = 0.f;
+    f16v l2;
+    if (want_sdf) mlp_sdf_net<TM>(W, s_b, A, lane, sdf, l2);
+
+    if (want_dx) {
+        // one-hot on the SDF row (row 0 = element 0 of lane half 0) back through L2 and the ReLU
+        Frag dH2;
+        frag_zero<TM>(dH2);
+        if (h == 0) frag_set<TM>(dH2, 0, 1.f);
+        f16v acc[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            acc_zero(acc[mt]);
+            mma(acc[mt], W.get(FR_B2 + mt * 2, lane), dH2);
+        }
+        Frag dH1[2][2];
+        masked_frags<TM>(acc, relu_mask<TM>(A.H1), dH1);
+        // d sdf / d feature = B1 dH1, in this lane's level order (register 8 ss + 2 qq + channel)
+        acc_zero(acc[0]);
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) mma(acc[0], W.get(FR_B1 + 2 * t2 + s2, lane), dH1[t2][s2]);
+        // kernel_input_backward's sum, levels ascending: levels 2 m, 2 m + 1 live in lane half
+        // m & 1 (lane_level), so the running sums change halves after every pair of levels
+        r[0] = 0.f; r[1] = 0.f; r[2] = 0.f;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int ss = m >> 2, qb = 2 * ((m >> 1) & 1), hh = m & 1;
+            float rn[3] = {r[0], r[1], r[2]};
+#pragma unroll
+            for (int qi = 0; qi < 2; ++qi) {
+                const int qq = qb + qi, k = 4 * ss + qq;
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch) {
+                    float g = acc[0][8 * ss + 2 * qq + ch];
+                    if constexpr (HALF) g = round_h(g);   // the fp16 Linear input gradient
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        if constexpr (HALF) rn[d] = round_h(rn[d] + round_h(g * dydx[k][d][ch]));
+                        else rn[d] = __builtin_fmaf(g, dydx[k][d][ch], rn[d]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const float other = __shfl_xor(rn[d], 32, 64);
+                r[d] = h == hh ? rn[d] : other;
+            }
+        }
+    }
+
+    if (want_rgb) {
+        // the colour pass's sigma net: fp32 reuses the SDF's unless the tile holds a point outside the box
+        if (HALF || !want_sdf || __any(inb && !inside)) {
+            if constexpr (HALF) {
+                A.X[0] = Xc[0];   // zero where !inside (never encoded)
+                A.X[1] = Xc[1];
+            } else if (!inside) {
+                frag_zero<TM>(A.X[0]);
+                frag_zero<TM>(A.X[1]);
+            }
+            float unused;
+            mlp_sdf_net<TM>(W, s_bc, A, lane, unused, l2);
+        }
+        // sh3 of the view direction ((0, 0, 0): only the constant term) and the frame's features, as
+        // sh_frag places them
+        Frag shf;
+        frag_zero<TM>(shf);
+        if constexpr (VIEW) {
+            const float vx = vdir[0], vy = vdir[1], vz = vdir[2];
+            const float xx = vx * vx, yy = vy * vy, zz = vz * vz;
+            if (h == 0) {
+                frag_set<TM>(shf, 0, SH_C0);
+                frag_set<TM>(shf, 1, -SH_C1 * vy);
+                frag_set<TM>(shf, 2, SH_C1 * vz);
+                frag_set<TM>(shf, 3, -SH_C1 * vx);
+                frag_set<TM>(shf, 4, SH_C2_4 * (xx - yy));
+            } else {
+                frag_set<TM>(shf, 0, SH_C2_0 * (vx * vy));
+                frag_set<TM>(shf, 1, SH_C2_1 * (vy * vz));
+                frag_set<TM>(shf, 2, SH_C2_2 * ((2.0f * zz - xx) - yy));
+                frag_set<TM>(shf, 3, SH_C2_3 * (vx * vz));
+            }
+        } else if (h == 0) {
+            frag_set<TM>(shf, 0, SH_C0);
+        }
+        if (h == 0 && ff) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) frag_set<TM>(shf, 5 + j, j < n_ff ? ff[j] : 0.f);
+        }
+        uint32_t m3 = 0, m4 = 0;
+        mlp_colour_net<TM>(W, s_bc, A, l2, shf, lane, logit, false, m3, m4);
+    }
+}
+
 template <typename TM, typename TT>
 __global__ __launch_bounds__(256) void k_query_field(FieldArgs a, QueryFieldArgs q) {
-    typedef typename FragT<TM>::T Frag;
     constexpr bool HALF = sizeof(TM) == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     TM *s_fr = reinterpret_cast<TM *>(smem);
@@ -133,118 +269,16 @@ __global__ __launch_bounds__(256) void k_query_field(FieldArgs a, QueryFieldArgs
 #pragma unroll
             for (int d = 0; d < 3; ++d) x[d] = q.pts[idx * 3 + d];
         }
-        // run_network's validity (:1244); the SDF and the gradient take the clipped point instead
-        const bool inside = fabsf(x[0]) <= 1.f && fabsf(x[1]) <= 1.f && fabsf(x[2]) <= 1.f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) x[d] = fminf(fmaxf(x[d], -1.f), 1.f);   // torch.clip(inputs, -1, 1)
-        const float x01[3] = {(x[0] + 1) / 2, (x[1] + 1) / 2, (x[2] + 1) / 2};
-        // colour alone: the zero embedding of a point outside the box needs no gather
-        const bool enc = inb && (want_sdf || inside);
-        Acts<TM> A;
-        Frag Xc[2];            // amp: the colour pass's features (half-kernel rounding)
-        float dydx[8][3][2];   // this lane's 8 levels (k = 4 ss + qq)
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const int lv = lane_level(ss, qq, h), k = 4 * ss + qq;
-                float v[2] = {0.f, 0.f}, vh[2] = {0.f, 0.f};
-#pragma unroll
-                for (int d = 0; d < 3; ++d) { dydx[k][d][0] = 0.f; dydx[k][d][1] = 0.f; }
-                if (enc && lv < (int)a.L)
-                    encode_level_dx<TT>(a, level_info(a, lv), x01, v, want_dx, dydx[k], want_rgb && inside, vh);
-                frag_set<TM>(A.X[ss], 2 * qq, v[0]);
-                frag_set<TM>(A.X[ss], 2 * qq + 1, v[1]);
-                if constexpr (HALF) {
-                    frag_set<TM>(Xc[ss], 2 * qq, vh[0]);
-                    frag_set<TM>(Xc[ss], 2 * qq + 1, vh[1]);
-                }
-            }
-        }
-        float sdf = 0.f;
-        f16v l2;
-        if (want_sdf) mlp_sdf_net<TM>(W, s_b, A, lane, sdf, l2);
-        if (q.sdf && inb && h == 0) q.sdf[idx] = sdf;
-
-        if (want_dx) {
-            // one-hot on the SDF row (row 0 = element 0 of lane half 0) back through L2 and the ReLU
-            Frag dH2;
-            frag_zero<TM>(dH2);
-            if (h == 0) frag_set<TM>(dH2, 0, 1.f);
-            f16v acc[2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                acc_zero(acc[mt]);
-                mma(acc[mt], W.get(FR_B2 + mt * 2, lane), dH2);
-            }
-            Frag dH1[2][2];
-            masked_frags<TM>(acc, relu_mask<TM>(A.H1), dH1);
-            // d sdf / d feature = B1 dH1, in this lane's level order (register 8 ss + 2 qq + channel)
-            acc_zero(acc[0]);
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) mma(acc[0], W.get(FR_B1 + 2 * t2 + s2, lane), dH1[t2][s2]);
-            // kernel_input_backward's sum, levels ascending: levels 2 m, 2 m + 1 live in lane half
-            // m & 1 (lane_level), so the running sums change halves after every pair of levels
-            float r[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int ss = m >> 2, qb = 2 * ((m >> 1) & 1), hh = m & 1;
-                float rn[3] = {r[0], r[1], r[2]};
-#pragma unroll
-                for (int qi = 0; qi < 2; ++qi) {
-                    const int qq = qb + qi, k = 4 * ss + qq;
-#pragma unroll
-                    for (int ch = 0; ch < 2; ++ch) {
-                        float g = acc[0][8 * ss + 2 * qq + ch];
-                        if constexpr (HALF) g = round_h(g);   // the fp16 Linear input gradient
-#pragma unroll
-                        for (int d = 0; d < 3; ++d) {
-                            if constexpr (HALF) rn[d] = round_h(rn[d] + round_h(g * dydx[k][d][ch]));
-                            else rn[d] = __builtin_fmaf(g, dydx[k][d][ch], rn[d]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    const float other = __shfl_xor(rn[d], 32, 64);
-                    r[d] = h == hh ? rn[d] : other;
-                }
-            }
-            if (inb && h == 0) {
+        float sdf, r[3], logit[3];
+        query_tile<TM, TT, false>(a, W, s_b, s_bc, x, inb, want_sdf, want_dx, want_rgb, q.ff, q.n_ff, nullptr, lane,
+                                  sdf, r, logit);
+        if (inb && h == 0) {
+            if (q.sdf) q.sdf[idx] = sdf;
+            if (want_dx) {
 #pragma unroll
                 for (int d = 0; d < 3; ++d) q.grad[idx * 3 + d] = 0.5f * r[d];   // x01 = (x + 1) / 2
             }
-        }
-
-        if (want_rgb) {
-            // the colour pass's sigma net: fp32 reuses the SDF's unless the tile holds a point outside the box
-            if (HALF || !want_sdf || __any(inb && !inside)) {
-                if constexpr (HALF) {
-                    A.X[0] = Xc[0];   // zero where !inside (never encoded)
-                    A.X[1] = Xc[1];
-                } else if (!inside) {
-                    frag_zero<TM>(A.X[0]);
-                    frag_zero<TM>(A.X[1]);
-                }
-                float unused;
-                mlp_sdf_net<TM>(W, s_bc, A, lane, unused, l2);
-            }
-            // sh3((0, 0, 0)): only the constant term; the frame's features as sh_frag places them
-            Frag shf;
-            frag_zero<TM>(shf);
-            if (h == 0) {
-                frag_set<TM>(shf, 0, SH_C0);
-                if (q.ff) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) frag_set<TM>(shf, 5 + j, j < q.n_ff ? q.ff[j] : 0.f);
-                }
-            }
-            float logit[3];
-            uint32_t m3 = 0, m4 = 0;
-            mlp_colour_net<TM>(W, s_bc, A, l2, shf, lane, logit, false, m3, m4);
-            if (inb && h == 0) {
+            if (want_rgb) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) q.rgb[idx * 3 + c] = 1.f / (1.f + expf(-logit[c]));
             }

@@ -2301,6 +2301,7 @@ __global__ __launch_bounds__(256) void k_query_sdf(FieldArgs a, QueryArgs q) {
 
 #include "field_query.h"    // the point query with gradient and colour (k_query_field)
 #include "field_render.h"   // the forward-only ray render (k_render_ctx, k_render, k_render_final)
+#include "field_view.h"     // the free-camera surface render (k_view_trace, k_view_march, k_view_shade)
 
 // end of the field pass: loss_acc[LOSS_FOLD_DST[k]] += sum of the LOSS_COPIES copies of slot k
 __device__ __forceinline__ void loss_fold(const float *__restrict__ part, float *__restrict__ loss_acc, int k) {
@@ -3019,4 +3020,94 @@ extern "C" int nof_render_rays(const nof_field_desc *d, const nof_render_out *o,
     if (rc) return rc;
     hipLaunchKernelGGL(nof::k_render_final, dim3(nof::div_up(a.R, 256)), dim3(256), 0, st, a, ro);
     return nof::check_launch("render_rays(final)");
+}
+
+namespace {
+// the surface render's workspace: per-ray records, the interval lists, the bracket records
+struct ViewWorkspace {
+    size_t vray, iv, brk, total;
+    ViewWorkspace(int n, int Kmax) {
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        size_t o = 0;
+        vray = o; o += al((size_t)n * nof::VRAY * 4);
+        iv = o; o += al((size_t)n * Kmax * 8);
+        brk = o; o += al((size_t)n * nof::VBRK * 4);
+        total = o;
+    }
+};
+}  // namespace
+
+extern "C" size_t nof_render_view_workspace_bytes(int32_t n, int32_t Kmax) {
+    return (n < 0 || Kmax <= 0) ? 0 : ViewWorkspace(n, Kmax).total;
+}
+
+extern "C" int nof_render_view(const nof_field_desc *d, const nof_view_desc *w, const nof_view_out *o, void *stream) {
+    // every refusal comes before the first HIP call, as in nof_render_rays
+    if (!d || !w || !o) return nof::set_error(NOF_EINVAL, "render_view: desc / view / out is NULL");
+    if (d->L == 0 || d->L > 16 || d->C != 2 || d->D != 3)
+        return nof::set_error(NOF_EINVAL, "render_view: needs D=3, C=2, 1<=L<=16 (got %u,%u,%u)", d->D, d->C, d->L);
+    const bool amp = d->mlp_dtype == NOF_F16 && d->table_dtype == NOF_F16;
+    if (!amp && !(d->mlp_dtype == NOF_F32 && d->table_dtype == NOF_F32))
+        return nof::set_error(NOF_EINVAL, "render_view: mlp/table dtype must both be f16 (amp) or both f32");
+    if (!d->table || !d->levels || !d->frags || !d->bias)
+        return nof::set_error(NOF_EINVAL, "render_view: table / levels / frags / bias is NULL");
+    if (d->n_ff < 0 || d->n_ff > 3 || (d->n_ff > 0 && !d->ff))
+        return nof::set_error(NOF_EINVAL, "render_view: frame_features must be 0..3 with ff set (got %d)", d->n_ff);
+    if (d->n_ff > 0 && (w->frame_id < 0 || w->frame_id >= w->n_frames))
+        return nof::set_error(NOF_EINVAL, "render_view: frame_id %d outside the %d frames", w->frame_id, w->n_frames);
+    if (d->Kmax <= 0) return nof::set_error(NOF_EINVAL, "render_view: Kmax=%d", d->Kmax);
+    if (w->H <= 0 || w->W <= 0 || (int64_t)w->H * w->W > INT32_MAX)
+        return nof::set_error(NOF_EINVAL, "render_view: bad image size H=%d W=%d", w->H, w->W);
+    if (!(w->K[0] != 0.f) || !(w->K[4] != 0.f))
+        return nof::set_error(NOF_EINVAL, "render_view: K has a zero focal length (fx=%g fy=%g)", w->K[0], w->K[4]);
+    if (w->n < 0 || w->n > (1 << 24)) return nof::set_error(NOF_EINVAL, "render_view: n=%d (0 <= n <= 2^24 rays a call)", w->n);
+    if (!w->pixels && (w->pixel0 < 0 || (int64_t)w->pixel0 + w->n > (int64_t)w->H * w->W))
+        return nof::set_error(NOF_EINVAL, "render_view: pixels %d..%lld leave the %dx%d image", w->pixel0,
+                              (long long)w->pixel0 + w->n, w->H, w->W);
+    if (!(w->step > 0.f) || w->max_steps <= 0 || w->max_steps > (1 << 20) || w->n_refine < 0 || w->n_refine > 64)
+        return nof::set_error(NOF_EINVAL, "render_view: step=%g (> 0), max_steps=%d (1..2^20), n_refine=%d (0..64)", w->step,
+                              w->max_steps, w->n_refine);
+    if (!w->occ || w->occ_n <= 0) return nof::set_error(NOF_EINVAL, "render_view: occ is NULL or occ_n=%d", w->occ_n);
+    if (w->n == 0) return NOF_OK;
+    if (!o->t || !o->depth || !o->normal || !o->rgb || !o->hit)
+        return nof::set_error(NOF_EINVAL, "render_view: out.t / depth / normal / rgb / hit is NULL");
+    if (!o->workspace)
+        return nof::set_error(NOF_EINVAL, "render_view: out.workspace is NULL (nof_render_view_workspace_bytes)");
+
+    nof::FieldArgs a{};
+    a.table = d->table; a.levels = (const float4 *)d->levels; a.L = d->L; a.mlp_in = (int)(d->L * d->C);
+    a.frags = d->frags; a.bias = d->bias;
+    const ViewWorkspace ws(w->n, d->Kmax);
+    char *wp = (char *)o->workspace;
+    nof::ViewArgs v{};
+    for (int i = 0; i < 12; ++i) v.c2w[i] = w->c2w[i];
+    v.fx = w->K[0]; v.fy = w->K[4]; v.cx = w->K[2]; v.cy = w->K[5];
+    v.W = w->W; v.pixels = w->pixels; v.pixel0 = w->pixel0; v.n = w->n;
+    v.step = w->step; v.max_steps = w->max_steps; v.n_refine = w->n_refine;
+    v.occ = w->occ; v.N = w->occ_n; v.Kmax = d->Kmax;
+    v.n_ff = d->n_ff;
+    v.ff = d->n_ff > 0 ? d->ff + (size_t)w->frame_id * d->n_ff : nullptr;
+    v.vray = (float *)(wp + ws.vray); v.iv = (float *)(wp + ws.iv); v.brk = (float *)(wp + ws.brk);
+    v.t = o->t; v.depth = o->depth; v.normal = o->normal; v.rgb = o->rgb; v.hit = o->hit;
+    v.index = o->index; v.tiles = o->tiles;
+
+    hipStream_t st = (hipStream_t)stream;
+    const int n_cu = cu_count();
+    hipLaunchKernelGGL(nof::k_view_trace, dim3(nof::div_up(v.n, 256)), dim3(256), 0, st, v);
+    int rc = nof::check_launch("render_view(trace)");
+    if (rc) return rc;
+    // a wave per ray, 4-wave blocks: persistent from 8 blocks per CU
+    const int mblocks = (int)std::min<int64_t>(((int64_t)v.n + 3) / 4, (int64_t)n_cu * 8);
+    const size_t esz = amp ? 2 : 4;
+    const size_t lds_m = (size_t)nof::VIEW_NFR * 64 * 8 * esz + 5 * 64 * 4;
+    if (amp) hipLaunchKernelGGL((nof::k_view_march<_Float16, __half>), dim3(mblocks), dim3(256), lds_m, st, a, v);
+    else hipLaunchKernelGGL((nof::k_view_march<float, float>), dim3(mblocks), dim3(256), lds_m, st, a, v);
+    rc = nof::check_launch("render_view(march)");
+    if (rc) return rc;
+    const int64_t ntile = ((int64_t)v.n + 31) / 32;
+    const int sblocks = (int)std::min<int64_t>((ntile + 3) / 4, (int64_t)n_cu * 2);
+    const size_t lds_s = (size_t)nof::N_FRAGS * 64 * 8 * esz + 5 * 64 * 4 + (amp ? 5 * 64 * 4 : 0);
+    if (amp) hipLaunchKernelGGL((nof::k_view_shade<_Float16, __half>), dim3(sblocks), dim3(256), lds_s, st, a, v);
+    else hipLaunchKernelGGL((nof::k_view_shade<float, float>), dim3(sblocks), dim3(256), lds_s, st, a, v);
+    return nof::check_launch("render_view(shade)");
 }

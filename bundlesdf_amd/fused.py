@@ -956,6 +956,82 @@ class FusedStep:
             out["valid"] = out["valid"].bool()
         return out
 
+    @torch.no_grad()
+    def render_view(self, c2w, K, H, W, frame_id=0, step=None, max_steps=512, n_refine=8, pixels=None, chunk=65536,
+                    stats=False):
+        """Surface render of the current field from a free camera (nof_render_view): per pixel the ray
+        of view.view_rays (c2w: camera-to-world in normalised space, the pool's GL convention; no
+        pose-array correction), the DDA over the trainer's occupancy grid, a front-to-back march of the
+        occupied length to the SDF's first sign change (step, widened to T / max_steps), n_refine
+        bisections and a linear interpolation, then normal and colour at the hit point. Returns a dict
+        of device tensors: "t" (ray parameter), "depth" (z-depth, normalised units) [H,W] float32,
+        "normal" (unit, query_field's gradient direction), "rgb" (sigmoid colour at view direction d
+        with frame `frame_id`'s features) [H,W,3] float32, "hit" [H,W] bool; a miss holds zeros. With
+        `pixels` (row-major indices [n] or (u, v) pairs [n,2]) the shapes are [n] / [n,3]. stats=True adds
+        "index" (the coarse sample of the crossing, -1 on a miss) and "tiles" (32-sample tiles marched),
+        int32. step defaults to half the truncation band of the current step: the SDF is supervised only
+        inside the band. The rays go through in launches of at most `chunk` (the interval buffer is
+        chunk x Kmax x 2 floats); the result does not depend on chunk. No training buffer is written
+        and captured graphs stay valid."""
+        from .view import pixel_indices
+        H, W = int(H), int(W)
+        dev = self.dev
+        pix = None if pixels is None else pixel_indices(H, W, pixels).to(torch.int32).to(dev).contiguous()
+        n = H * W if pix is None else int(pix.numel())
+        shape = (H, W) if pix is None else (n,)
+        if step is None:
+            step = 0.5 * truncation(self.cfg, self.global_step)
+        out = {"t": torch.empty(n, device=dev), "depth": torch.empty(n, device=dev),
+               "normal": torch.empty(n, 3, device=dev), "rgb": torch.empty(n, 3, device=dev),
+               "hit": torch.empty(n, dtype=torch.uint8, device=dev)}
+        if stats:
+            out.update(index=torch.empty(n, dtype=torch.int32, device=dev),
+                       tiles=torch.empty(n, dtype=torch.int32, device=dev))
+        V = _lib.ViewDesc()
+        V.c2w[:] = np.asarray(c2w, np.float64).astype(np.float32).reshape(16).tolist()
+        V.K[:] = np.asarray(K, np.float64).astype(np.float32).reshape(9).tolist()
+        V.H, V.W = H, W
+        V.step, V.max_steps, V.n_refine = float(step), int(max_steps), int(n_refine)
+        V.frame_id, V.n_frames = int(frame_id), self.F
+        V.occ, V.occ_n = self.occ.data_ptr(), self.Nocc
+        D = _lib.FieldDesc()
+        D.L, D.C, D.D, D.Kmax = self.L, self.C, 3, self.Kmax
+        D.table = (self.emb16 if self.amp else self.P).data_ptr()
+        D.levels = self.levels.data_ptr()
+        D.table_dtype = D.mlp_dtype = _F16 if self.amp else _F32
+        D.frags, D.bias = self.frags.data_ptr(), self.bias.data_ptr()
+        D.n_ff = self.n_ff
+        if self.n_ff:
+            D.ff = self.P.data_ptr() + 4 * self.feat_off
+        if n > 0:
+            self.wait_exchange()
+            self.pack_mlp()
+            chunk = max(1, min(int(chunk), 1 << 24))
+            L = _lib.lib()
+            st = _lib.stream_of(self.P)
+            m_max = min(chunk, n)
+            vb = getattr(self, "_view_ws", None)
+            need = int(L.nof_render_view_workspace_bytes(m_max, self.Kmax))
+            if vb is None or vb.numel() < need:
+                vb = self._view_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            for lo in range(0, n, chunk):
+                m = min(chunk, n - lo)
+                V.n, V.pixel0 = m, lo if pix is None else 0
+                V.pixels = None if pix is None else pix.data_ptr() + 4 * lo
+                O = _lib.ViewOut(t=out["t"].data_ptr() + 4 * lo, depth=out["depth"].data_ptr() + 4 * lo,
+                                 normal=out["normal"].data_ptr() + 12 * lo, rgb=out["rgb"].data_ptr() + 12 * lo,
+                                 hit=out["hit"].data_ptr() + lo, workspace=vb.data_ptr())
+                if stats:
+                    O.index, O.tiles = out["index"].data_ptr() + 4 * lo, out["tiles"].data_ptr() + 4 * lo
+                _lib.check(L.nof_render_view(_lib.ctypes.byref(D), _lib.ctypes.byref(V), _lib.ctypes.byref(O), st),
+                           "render_view")
+        else:   # nothing to launch: the arguments are still checked
+            V.n = 0
+            _lib.check(_lib.lib().nof_render_view(_lib.ctypes.byref(D), _lib.ctypes.byref(V),
+                                                  _lib.ctypes.byref(_lib.ViewOut()), None), "render_view")
+        out["hit"] = out["hit"].bool()
+        return {k: v.reshape(*shape, *v.shape[1:]) for k, v in out.items()}
+
     def refresh_half_table(self):
         """Re-derive the fp16 table mirror after the fp32 table was written from outside (load_weights,
         reset_state). Under the sharded exchange the rank's mirror shard is re-copied as well: the

@@ -573,6 +573,24 @@ class NerfRunner:
             gt_depth_full[uvs[:, 1], uvs[:, 0]] = rays[:, 6]
         return rgb_full, depth_full, ray_mask_full, gt_rgb_full, gt_depth_full, extras
 
+    def render_view(self, c2w, K=None, H=None, W=None, metres=False, **kw):
+        """The field's surface seen from a free camera (FusedStep.render_view): c2w is a camera-to-world
+        pose in normalised space, in the convention of self.poses (no pose-array correction is applied);
+        K, H, W default to the runner's own. Returns numpy images {"t", "depth" [H,W] float32, "normal",
+        "rgb" [H,W,3] float32, "hit" [H,W] bool} ([n] / [n,3] with pixels=...); misses hold zeros.
+        metres=True divides t and depth by sc_factor. No reference counterpart: the reference renders
+        an extracted mesh with pyrender (offscreen_renderer.py)."""
+        K = self.K if K is None else K
+        H = self.H if H is None else H
+        W = self.W if W is None else W
+        kw.setdefault("step", 0.5 * self.get_truncation())
+        r = self.trainer.render_view(c2w, K, H, W, **kw)
+        out = {k: v.cpu().numpy() for k, v in r.items()}
+        if metres:
+            sc = np.float32(self.cfg["sc_factor"])
+            out["t"], out["depth"] = out["t"] / sc, out["depth"] / sc
+        return out
+
     def get_truncation(self):
         """nerf_runner.py:661-674: the truncation band of the current step (linear / exp
         annealing from trunc_start when trunc_decay_type is set), times sc_factor."""

@@ -352,6 +352,60 @@ int nof_query_field(const void *table, int32_t table_dtype, const float *level_t
                     const float *ff, int32_t n_frames, int32_t n_ff, int32_t frame_id, float *sdf, float *grad,
                     float *rgb, void *stream);
 
+/* Free-camera surface render: depth, normal and colour of the field's zero level set seen from any
+ * camera (no pool ray, no frame depth; no reference counterpart — the reference renders an extracted
+ * mesh with pyrender, offscreen_renderer.py). Per pixel, fp32 with every operation rounded on its own:
+ *   ray      dir_cam = ((u - cx) / fx, -((v - cy) / fy), -1), v^ = dir_cam / |dir_cam|, o = c2w[:3,3],
+ *            d = R v^ (the pool's convention; no pose-array correction);
+ *   trace    the dense-occupancy DDA of nof_octree_ray_trace over occ, at most Kmax intervals, each
+ *            entry clamped to t >= 0; T = their summed length; no interval: a miss;
+ *   march    step_eff = max(step, T / max_steps), n = ceil(T / step_eff) samples at occupied length
+ *            (k + 0.5) step_eff, mapped to t_k by the occupied-voxel sampler's interval walk (a length
+ *            past the walk reads the last exit); SDF as nof_query_sdf (the same bits), front to back;
+ *   crossing the first k with sdf_k <= 0: k = 0 gives t* = t_0, else the bracket [t_{k-1}, t_k]; none:
+ *            a miss;
+ *   refine   n_refine bisections (midpoint 0.5 (lo + hi), keeping sdf_lo > 0 >= sdf_hi), then
+ *            t* = lo + (hi - lo) sdf_lo / (sdf_lo - sdf_hi);
+ *   outputs  at x* = o + t* d. */
+typedef struct {
+    float c2w[16];          /* camera-to-world, row-major, normalised space (NerfRunner.poses) */
+    float K[9];             /* intrinsics, row-major */
+    int32_t H, W;
+    const int32_t *pixels;  /* device, optional [n]: row-major pixel index v W + u of each ray; the caller keeps
+                               every index in [0, H W) */
+    int32_t n;              /* rays of this call (<= 2^24) */
+    int32_t pixel0;         /* pixels NULL: ray i is pixel pixel0 + i, pixel0 + n <= H W */
+    float step;             /* coarse step along the occupied length (> 0), normalised units */
+    int32_t max_steps;      /* upper bound of samples per ray: the step widens to T / max_steps */
+    int32_t n_refine;       /* bisection steps on the bracket (0..64) */
+    int32_t frame_id;       /* the frame whose features feed the colour net (desc n_ff > 0) */
+    int32_t n_frames;       /* rows of desc->ff */
+    int32_t occ_n;
+    const uint8_t *occ;     /* device [occ_n^3] occupancy, x fastest (as nof_trace_rays) */
+} nof_view_desc;
+
+typedef struct {
+    float *t;          /* [n] ray parameter of the hit (distance along the unit direction), 0 on a miss */
+    float *depth;      /* [n] t |v^_z|: z-depth in normalised units, as depth images / pool column 6 */
+    float *normal;     /* [n,3] nof_query_field's gradient at x* over its norm (a zero gradient stays zero) */
+    float *rgb;        /* [n,3] sigmoid of the colour net on x*'s geometry features, sh3(d) and the frame's
+                          features, with nof_query_field's colour pass */
+    uint8_t *hit;      /* [n] 1 on a hit; a miss writes zeros everywhere */
+    int32_t *index;    /* optional [n]: the coarse sample k of the crossing, -1 on a miss */
+    int32_t *tiles;    /* optional [n]: 32-sample tiles the march evaluated */
+    void *workspace;   /* nof_render_view_workspace_bytes(n, desc->Kmax) bytes of scratch */
+} nof_view_out;
+
+size_t nof_render_view_workspace_bytes(int32_t n, int32_t Kmax);
+
+/* Reads of desc: Kmax, table, levels, L, C, D, the dtypes, n_ff, ff, frags, bias; everything else is
+ * ignored. Launches k_view_trace (a thread per ray: ray, DDA, interval list), k_view_march (a wave per
+ * ray over its 32-sample tiles, stopping at the first crossing) and k_view_shade (a wave per 32 rays:
+ * bisection, gradient, colour net). No atomics: two calls on the same inputs are bit-identical, and a
+ * ray's result does not depend on the rays rendered with it. Everything is validated before the first
+ * HIP call; n == 0 returns NOF_OK with no launch. */
+int nof_render_view(const nof_field_desc *desc, const nof_view_desc *view, const nof_view_out *out, void *stream);
+
 /* Pose corrections on the device (replaces PoseArray.get_matrices,
  * nerf_helpers.py:127-154, and tf = T @ c2w, nerf_runner.py:1050-1052, with
  * their autograd). data [F,6] f32 (PoseArray.data); c2w [F,4,4] f32;
