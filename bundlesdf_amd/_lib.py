@@ -73,6 +73,8 @@ _SIGNATURES = {
     "nof_raster_faces": ([_p, _p, _i64, _p, _p, _i32, _i32, ctypes.c_double, ctypes.c_double, _p, _p], _int),
     "nof_texture_hits": ([_p, _i32, _i32, _p, _f32, _p, _p, _p, _p, _p, _p, _p], _int),
     "nof_texture_accumulate": ([_p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p], _int),
+    "nof_vertex_color_accumulate": ([_p, _i32, _i32, _p, _f32, _p, _p, _p, _p, _p, _i64, ctypes.c_double, _p, _p, _p, _p,
+                                     _p], _int),
     "nof_segment_mean": ([_p, _i32, _p, _p, _i32, _p, _p], _int),
     "nof_dbscan": ([_p, _i32, ctypes.c_double, _i32, _p, _p, _p, _p, _p], _int),
 }

@@ -18,6 +18,18 @@
 //  k_tex_first /   texel = round-half-even(uv) flattened with the reference's
 //  k_tex_add       row stride (W-1) (nerf_runner.py:1524-1531); the first
 //                  hit (pixel order) of each texel adds its colour and weight 1.
+//
+// Vertex colours from the training images (SURVEY §8f row 2,
+// NerfRunner.mesh_vertex_color_from_train_images, nerf_runner.py:1431-1464): the
+// reference back-projects every frame's depth image, builds a cKDTree over
+// the points and queries it once per vertex. Here:
+//
+//  k_vertex_color  one lane per vertex: the nearest back-projected pixel of
+//                  the z-buffer inside the screen window that bounds every
+//                  candidate within `radius` (see the kernel), its colour
+//                  added to the vertex's f64 sum and 1 to its count.
+#include <cmath>
+
 #include "nof_device.h"
 
 #pragma clang fp contract(off)
@@ -69,6 +81,15 @@ __global__ __launch_bounds__(256) void k_raster(const float *__restrict__ V, con
             const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)f;
             atomicMin(&zbuf[(size_t)py * W + px], key);
         }
+}
+
+// Pixel (px, py) of depth z in the object frame: depth2xyzmap (Utils.py:219-231, f64 arithmetic,
+// f32 result) followed by cam_in_ob (`inv`) in f64.
+__device__ __forceinline__ void backproject(const Cam &inv, int px, int py, float z, double p[3]) {
+    const float xc = (float)(((double)px - inv.cx) * (double)z / inv.fx);
+    const float yc = (float)(((double)py - inv.cy) * (double)z / inv.fy);
+    const double pc[3] = {xc, yc, (double)z};
+    for (int k = 0; k < 3; ++k) p[k] = ((inv.R[3 * k] * pc[0] + inv.R[3 * k + 1] * pc[1]) + inv.R[3 * k + 2] * pc[2]) + inv.t[k];
 }
 
 // Closest point of triangle (a, b, c) to p (Voronoi-region walk, f64).
@@ -123,12 +144,8 @@ __global__ __launch_bounds__(256) void k_hits(const unsigned long long *__restri
     if (!(z >= min_depth)) return;
     const int64_t f = (int64_t)(key & 0xffffffffull);
     const int py = i / W, px = i - py * W;
-    // depth2xyzmap (Utils.py:219-231): f64 arithmetic, f32 result
-    const float xc = (float)(((double)px - inv.cx) * (double)z / inv.fx);
-    const float yc = (float)(((double)py - inv.cy) * (double)z / inv.fy);
-    const double pc[3] = {xc, yc, (double)z};
     double p[3];
-    for (int k = 0; k < 3; ++k) p[k] = ((inv.R[3 * k] * pc[0] + inv.R[3 * k + 1] * pc[1]) + inv.R[3 * k + 2] * pc[2]) + inv.t[k];
+    backproject(inv, px, py, z, p);
     double a[3], b[3], c[3], q[3];
     for (int k = 0; k < 3; ++k) {
         a[k] = V[F[f * 3] * 3 + k];
@@ -138,6 +155,89 @@ __global__ __launch_bounds__(256) void k_hits(const unsigned long long *__restri
     closest_on_tri(p, a, b, c, q);
     for (int k = 0; k < 3; ++k) loc[(size_t)i * 3 + k] = (float)q[k];
     face[i] = f;
+}
+
+// Pixel range [lo, hi] that x / z * f + c can reach for x in [x0, x1], z in [z0, z1], z0 > 0: the
+// expression is monotone in x and in z, so its extremes are at the four corners. Floor / ceil,
+// one more pixel each way, clamped to [0, n - 1]; false where nothing is left (or a NaN came in).
+__device__ __forceinline__ bool pixel_range(double f, double c, double x0, double x1, double z0, double z1, int n,
+                                            int &lo, int &hi) {
+    const double a = f * x0 / z0 + c, b = f * x0 / z1 + c, d = f * x1 / z0 + c, e = f * x1 / z1 + c;
+    const double l = fmax(floor(fmin(fmin(a, b), fmin(d, e))) - 1.0, 0.0);
+    const double h = fmin(ceil(fmax(fmax(a, b), fmax(d, e))) + 1.0, (double)(n - 1));
+    if (!(l <= h)) return false;
+    lo = (int)l;
+    hi = (int)h;
+    return true;
+}
+
+// One lane per vertex. The candidates are k_hits' pixels (a face, the mask, z >= min_depth) and a
+// candidate's point is k_hits' p (backproject). The match is the candidate with the smallest
+// d2 = (dx*dx + dy*dy) + dz*dz, ties to the lowest pixel index (the window is walked in pixel
+// order and only a strictly smaller d2 replaces the best), accepted where sqrt(d2) <= radius.
+//
+// Search window. In the camera frame the vertex is (Xv, Yv, Zv) and a candidate is
+// (xc, yc, z) with xc = (px - cx) * z / fx, so px = fx * xc / z + cx. cam_in_ob is rigid, so a
+// candidate within r = radius of the vertex has |xc - Xv| <= r, |yc - Yv| <= r, |z - Zv| <= r, and
+// z >= min_depth > 0 besides. fx * x / z + cx is monotone in x and in z for z > 0, hence px lies
+// between the min and the max of that expression over the corners of [Xv - r, Xv + r] x
+// [max(Zv - r, min_depth), Zv + r], and py likewise. The range is floored / ceiled and widened
+// by one pixel: the f32 rounding of xc and yc moves px by 2^-24 |px - cx|, and ob_in_cam being
+// only the computed inverse of cam_in_ob (or a rotation orthonormal only to f32) moves it by
+// about 1e-7 of the window, both far below a pixel. Zv + r < min_depth or a range that misses the
+// image means there is no candidate within r, and pixels of the window that lie beyond r are
+// rejected by the distance test itself: what is reported never depends on the window.
+//
+// One vertex is one lane's, so the sums are plain read-modify-writes: no atomics, and the
+// result does not depend on the launch shape.
+__global__ __launch_bounds__(256) void k_vertex_color(const unsigned long long *__restrict__ zbuf, int H, int W,
+                                                      const uint8_t *__restrict__ mask, float min_depth,
+                                                      const float *__restrict__ colors, Cam inv, Cam c,
+                                                      const float *__restrict__ V, int64_t nV, double radius,
+                                                      double *__restrict__ color_sum, int32_t *__restrict__ count,
+                                                      int32_t *__restrict__ nearest,
+                                                      double *__restrict__ nearest_dist) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nV) return;
+    const double vx = V[j * 3], vy = V[j * 3 + 1], vz = V[j * 3 + 2];
+    const double Xv = ((c.R[0] * vx + c.R[1] * vy) + c.R[2] * vz) + c.t[0];
+    const double Yv = ((c.R[3] * vx + c.R[4] * vy) + c.R[5] * vz) + c.t[1];
+    const double Zv = ((c.R[6] * vx + c.R[7] * vy) + c.R[8] * vz) + c.t[2];
+    const double z0 = fmax(Zv - radius, (double)min_depth), z1 = Zv + radius;
+    double best = __builtin_inf();
+    int best_i = -1;
+    int u0, u1, v0, v1;
+    if (z0 <= z1 && pixel_range(c.fx, c.cx, Xv - radius, Xv + radius, z0, z1, W, u0, u1) &&
+        pixel_range(c.fy, c.cy, Yv - radius, Yv + radius, z0, z1, H, v0, v1)) {
+        for (int py = v0; py <= v1; ++py)
+            for (int px = u0; px <= u1; ++px) {
+                const int i = py * W + px;
+                const unsigned long long key = zbuf[i];
+                if (key == ~0ull || !mask[i]) continue;
+                const float z = __uint_as_float((uint32_t)(key >> 32));
+                if (!(z >= min_depth)) continue;
+                double p[3];
+                backproject(inv, px, py, z, p);
+                const double dx = p[0] - vx, dy = p[1] - vy, dz = p[2] - vz;
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 < best) {
+                    best = d2;
+                    best_i = i;
+                }
+            }
+    }
+    const double dist = sqrt(best);
+    const bool ok = best_i >= 0 && dist <= radius;
+    if (ok) {
+        const float *col = colors + (size_t)best_i * 3;
+        double *s = color_sum + j * 3;
+        s[0] += (double)col[0];
+        s[1] += (double)col[1];
+        s[2] += (double)col[2];
+        count[j] += 1;
+    }
+    if (nearest) nearest[j] = ok ? best_i : -1;
+    if (nearest_dist) nearest_dist[j] = ok ? dist : __builtin_inf();
 }
 
 __device__ __forceinline__ int64_t texel_flat(const float *uv, int TW) {
@@ -225,6 +325,30 @@ int nof_texture_accumulate(const float *uvs, const int32_t *pix, int64_t n_hits,
     hipLaunchKernelGGL(k_tex_add, dim3(div_up(n_hits, 256)), dim3(256), 0, s, uvs, pix, n_hits, colors, tex_h, tex_w,
                        n_first, first, tex, weight);
     return check_launch("texture_accumulate");
+}
+
+int nof_vertex_color_accumulate(const uint64_t *zbuf, int32_t H, int32_t W, const uint8_t *mask, float min_depth,
+                                const float *colors, const double *cam_in_ob, const double *ob_in_cam, const double *K,
+                                const float *V, int64_t n_vertices, double radius, double *color_sum, int32_t *count,
+                                int32_t *nearest, double *nearest_dist, void *stream) {
+    const char *fn = "vertex_color_accumulate";
+    if (H <= 0 || W <= 0) return set_error(NOF_EINVAL, "%s: H=%d, W=%d must be positive", fn, H, W);
+    if ((int64_t)H * W >= (1ll << 31)) return set_error(NOF_EINVAL, "%s: H*W=%lld must be below 2^31", fn, (long long)H * W);
+    if (n_vertices < 0 || n_vertices >= (1ll << 31))
+        return set_error(NOF_EINVAL, "%s: n_vertices=%lld must be in [0, 2^31)", fn, (long long)n_vertices);
+    if (!std::isfinite(radius) || radius <= 0) return set_error(NOF_EINVAL, "%s: radius=%g must be finite and > 0", fn, radius);
+    if (!(min_depth > 0)) return set_error(NOF_EINVAL, "%s: min_depth=%g must be > 0", fn, (double)min_depth);
+    const struct { const void *p; const char *name; bool need; } ptrs[] = {
+        {zbuf, "zbuf", true}, {mask, "mask", true}, {colors, "colors", true}, {cam_in_ob, "cam_in_ob", true},
+        {ob_in_cam, "ob_in_cam", true}, {K, "K", true}, {V, "V", n_vertices > 0},
+        {color_sum, "color_sum", n_vertices > 0}, {count, "count", n_vertices > 0}};
+    for (const auto &a : ptrs)
+        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (n_vertices == 0) return 0;
+    hipLaunchKernelGGL(k_vertex_color, dim3(div_up(n_vertices, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long *)zbuf, H, W, mask, min_depth, colors, make_cam(cam_in_ob, K),
+                       make_cam(ob_in_cam, K), V, n_vertices, radius, color_sum, count, nearest, nearest_dist);
+    return check_launch(fn);
 }
 
 }  // extern "C"

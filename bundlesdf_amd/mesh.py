@@ -106,7 +106,8 @@ class Mesh:
         self.uv = None          # [V,2] texture coordinates (texture.unwrap)
         self.texture = None     # [H,W,3] uint8 image (texture.bake_texture), row 0 = top
         self.vertex_normals = None   # [V,3] float, unit length (NerfRunner.mesh_vertex_normals_from_network)
-        self.vertex_colors = None    # [V,3] uint8 (NerfRunner.mesh_vertex_color_from_network)
+        self.vertex_colors = None    # [V,3] uint8 (NerfRunner.mesh_vertex_color_from_network / _from_train_images)
+        self.vertex_color_counts = None   # [V] int32: frames that coloured the vertex (_from_train_images)
 
     @property
     def face_normals(self):
@@ -131,6 +132,7 @@ class Mesh:
         m.texture = None if self.texture is None else self.texture.copy()
         m.vertex_normals = None if self.vertex_normals is None else self.vertex_normals.copy()
         m.vertex_colors = None if self.vertex_colors is None else self.vertex_colors.copy()
+        m.vertex_color_counts = None if self.vertex_color_counts is None else self.vertex_color_counts.copy()
         return m
 
     def _take_vertex_rows(self, rows):
@@ -139,6 +141,8 @@ class Mesh:
             self.vertex_normals = np.asarray(self.vertex_normals)[rows]
         if self.vertex_colors is not None:
             self.vertex_colors = np.asarray(self.vertex_colors)[rows]
+        if self.vertex_color_counts is not None:
+            self.vertex_color_counts = np.asarray(self.vertex_color_counts)[rows]
 
     def merge_vertices(self):
         """Weld vertices at identical positions (marching_cubes output already shares them)."""

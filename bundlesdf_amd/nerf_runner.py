@@ -214,6 +214,8 @@ def _check_supported(cfg):
         raise NotImplementedError(f"trunc_decay_type {cfg['trunc_decay_type']!r}")
     if cfg.get("mode", "sdf") != "sdf":
         raise NotImplementedError("fused MI355X path: mode 'sdf' only")
+    if cfg.get("mesh_vertex_color_source", "network") not in ("network", "train_images"):   # not a reference key
+        raise ValueError(f"mesh_vertex_color_source {cfg['mesh_vertex_color_source']!r}: 'network' or 'train_images'")
 
 
 HOOK_KEYS = ("i_weights", "i_img", "i_print", "i_mesh", "i_pose")   # train_loop's order (:764-851)
@@ -505,7 +507,10 @@ class NerfRunner:
             return
         if self.cfg.get("mesh_vertex_attributes"):   # not a reference key: off unless asked for
             self.mesh_vertex_normals_from_network(mesh)
-            self.mesh_vertex_color_from_network(mesh)
+            if self.cfg.get("mesh_vertex_color_source", "network") == "train_images":
+                self.mesh_vertex_color_from_train_images(mesh, fill_from_network=True)
+            else:
+                self.mesh_vertex_color_from_network(mesh)
             self.mesh = mesh.copy()
         path = self._save_path(f"step_{self.global_step:07d}_mesh_normalized_space.obj")
         mesh.export(path)
@@ -648,6 +653,16 @@ class NerfRunner:
         rgb = self.trainer.query_field(np.asarray(mesh.vertices, np.float32), sdf=False, colour=True, frame_id=0)
         mesh.vertex_colors = (rgb["colour"].cpu().numpy() * 255).astype(np.uint8)
         return mesh
+
+    def mesh_vertex_color_from_train_images(self, mesh, fill_from_network=False):
+        """nerf_runner.py:1431-1464: the colour every vertex of `mesh` (normalised space) has in the
+        training frames, on the device (bundlesdf_amd.texture): per frame the nearest back-projected
+        pixel of the mesh's depth image within 0.002 * sc_factor, averaged over the frames that have
+        one. Sets mesh.vertex_colors (uint8 [V,3]) and mesh.vertex_color_counts (int32 [V], frames
+        per vertex) and returns the mesh. A vertex no frame sees is (0, 0, 0), or with
+        fill_from_network (not in the reference) the colour mesh_vertex_color_from_network gives it."""
+        from .texture import mesh_vertex_color_from_train_images
+        return mesh_vertex_color_from_train_images(self, mesh, fill_from_network=fill_from_network)
 
     def mesh_vertex_normals_from_network(self, mesh):
         """Sets mesh.vertex_normals (float [V,3]) to the unit-length SDF gradient of the field at every

@@ -17,6 +17,12 @@ below is a deterministic per-face atlas — faces in pairs, each pair a grid
 cell split along its diagonal, an inset of about one texel — so parity with
 xatlas' charts is out of reach (PARITY UNPINNED for the atlas); everything
 after the UVs is checked against oracle/texture.py on identical UVs.
+
+Vertex colours from the same frames (SURVEY §8f row 2,
+NerfRunner.mesh_vertex_color_from_train_images, nerf_runner.py:1431-1464):
+vertex_colors_from_images is the same frame loop with two launches,
+nof_raster_faces and nof_vertex_color_accumulate (the nearest back-projected
+pixel per vertex, in place of the reference's cKDTree over the frame's points).
 """
 import numpy as np
 import torch
@@ -94,6 +100,76 @@ def bake_texture(mesh, rgbs_raw, masks, cvcam_in_obs, K, H, W, min_depth, zfar, 
     return out.flip(0).cpu().numpy()
 
 
+def _cvcam_in_obs(runner):
+    """OpenCV camera-in-object poses of the runner's frames: c2w_array with the learned pose
+    corrections where there are any, times inv(GLCAM_IN_CVCAM) (nerf_runner.py:1437-1448, :1488-1500)."""
+    ids = torch.arange(len(runner.images), device=runner.device)
+    with torch.no_grad():
+        tf = runner.c2w_array[ids]
+        if runner.models["pose_array"] is not None:
+            tf = runner.models["pose_array"].get_matrices(ids) @ tf
+    tf = tf.cpu().numpy()
+    return np.stack([tf[i] @ np.linalg.inv(GLCAM_IN_CVCAM) for i in range(len(tf))])
+
+
+def vertex_colors_from_images(vertices, faces, images, masks, cvcam_in_obs, K, H, W, min_depth, zfar, radius,
+                              device=None):
+    """NerfRunner.mesh_vertex_color_from_train_images (nerf_runner.py:1431-1464) on the device:
+    per frame the mesh's depth (nof_raster_faces, znear 0.1) and nof_vertex_color_accumulate, which
+    adds to every vertex the colour of its nearest back-projected masked pixel of depth >=
+    min_depth where that lies within `radius` (the reference's cKDTree query, searched in the
+    screen window around the vertex's projection). images [N,H,W,3] (added as float32), masks
+    [N,H,W(,1)], cvcam_in_obs [N,4,4] (OpenCV camera in object), K [3,3]. Returns (colors uint8
+    [Nv,3] = clip(sum / count * 255, 0, 255) truncated, in float64 as the reference computes it;
+    count int32 [Nv], the number of frames that coloured the vertex). A vertex with count 0 gets
+    (0, 0, 0): the reference's 0/0 -> NaN -> uint8 cast is undefined."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    L = _lib.lib()
+    V = torch.as_tensor(np.asarray(vertices, np.float32), device=dev).contiguous()
+    Fc = torch.as_tensor(np.asarray(faces, np.int64), device=dev).contiguous()
+    Kd = np.ascontiguousarray(np.asarray(K, np.float64))
+    nV = len(V)
+    csum = torch.zeros((nV, 3), dtype=torch.float64, device=dev)
+    cnt = torch.zeros(nV, dtype=torch.int32, device=dev)
+    zbuf = torch.empty(H * W, dtype=torch.int64, device=dev)
+    st = _lib.stream_of(V)
+    for i in range(len(images)):
+        cam_in_ob = np.ascontiguousarray(np.asarray(cvcam_in_obs[i], np.float64))
+        ob_in_cam = np.ascontiguousarray(np.linalg.inv(cam_in_ob))
+        _lib.check(L.nof_raster_faces(_lib.ptr(V), _lib.ptr(Fc), len(Fc), ob_in_cam.ctypes.data_as(_lib._p),
+                                      Kd.ctypes.data_as(_lib._p), H, W, 0.1, float(zfar), _lib.ptr(zbuf), st),
+                   "raster_faces")
+        m = torch.as_tensor(np.asarray(masks[i]).reshape(H, W).astype(bool).astype(np.uint8), device=dev)
+        img = torch.as_tensor(np.asarray(images[i], np.float32).reshape(H * W, 3), device=dev).contiguous()
+        _lib.check(L.nof_vertex_color_accumulate(_lib.ptr(zbuf), H, W, _lib.ptr(m), float(min_depth), _lib.ptr(img),
+                                                 cam_in_ob.ctypes.data_as(_lib._p), ob_in_cam.ctypes.data_as(_lib._p),
+                                                 Kd.ctypes.data_as(_lib._p), _lib.ptr(V), nV, float(radius),
+                                                 _lib.ptr(csum), _lib.ptr(cnt), None, None, st),
+                   "vertex_color_accumulate")
+    count = cnt.cpu().numpy()
+    csum = csum.cpu().numpy()
+    seen = count > 0
+    colors = np.zeros((nV, 3), np.float64)
+    colors[seen] = np.clip(csum[seen] / count[seen].astype(np.float64).reshape(-1, 1) * 255, 0, 255)
+    return colors.astype(np.uint8), count
+
+
+def mesh_vertex_color_from_train_images(runner, mesh, fill_from_network=False):
+    """nerf_runner.py:1431-1464 for a NerfRunner: sets mesh.vertex_colors (uint8 [Nv,3]) and
+    mesh.vertex_color_counts (int32 [Nv]) from the training frames and returns the mesh (normalised
+    space). fill_from_network gives the vertices no frame coloured the network's colour."""
+    sc = runner.cfg["sc_factor"]
+    colors, count = vertex_colors_from_images(mesh.vertices, mesh.faces, runner.images, runner.masks,
+                                              _cvcam_in_obs(runner), runner.K, runner.H, runner.W, 0.1 * sc,
+                                              runner.cfg["far"] * sc, 0.002 * sc, runner.device)
+    if fill_from_network and (count == 0).any():
+        net = np.asarray(runner.mesh_vertex_color_from_network(mesh).vertex_colors)
+        colors[count == 0] = net[count == 0]
+    mesh.vertex_colors = colors
+    mesh.vertex_color_counts = count
+    return mesh
+
+
 def mesh_texture_from_train_images(runner, mesh, rgbs_raw, train_texture=False, tex_res=1024):
     """nerf_runner.py:1467-1541 for a NerfRunner: poses with the learned corrections,
     merge/dedupe, unwrap, bake; returns the unwrapped mesh with .uv and .texture."""
@@ -101,13 +177,7 @@ def mesh_texture_from_train_images(runner, mesh, rgbs_raw, train_texture=False, 
         raise NotImplementedError("mesh_texture_from_train_images: train_texture=True is not implemented")
     assert len(runner.images) == len(rgbs_raw)
     dev = runner.device
-    ids = torch.arange(len(runner.images), device=dev)
-    with torch.no_grad():
-        tf = runner.c2w_array[ids]
-        if runner.models["pose_array"] is not None:
-            tf = runner.models["pose_array"].get_matrices(ids) @ tf
-    tf = tf.cpu().numpy()
-    cvcam_in_obs = np.stack([tf[i] @ np.linalg.inv(GLCAM_IN_CVCAM) for i in range(len(tf))])
+    cvcam_in_obs = _cvcam_in_obs(runner)
     mesh.merge_vertices()
     mesh.remove_duplicate_faces()
     mesh = unwrap(mesh, tex_res)

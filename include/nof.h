@@ -575,7 +575,9 @@ int nof_dbscan(const double *points, int32_t n, double eps, int32_t min_samples,
 
 /* ------------------------------------------------------------------ group 5
  * Texture baking from the training images, the device
- * path of NerfRunner.mesh_texture_from_train_images (nerf_runner.py:1467-1541).
+ * path of NerfRunner.mesh_texture_from_train_images (nerf_runner.py:1467-1541),
+ * and vertex colours from the same images (SURVEY §8f row 2,
+ * NerfRunner.mesh_vertex_color_from_train_images, nerf_runner.py:1431-1464).
  */
 
 /* Depth + face-id z-buffer of a mesh seen by an OpenCV pinhole camera (the
@@ -604,6 +606,29 @@ int nof_texture_hits(const uint64_t *zbuf, int32_t H, int32_t W, const uint8_t *
  * on entry and on return. */
 int nof_texture_accumulate(const float *uvs, const int32_t *pix, int64_t n_hits, const float *colors, int32_t tex_h,
                            int32_t tex_w, int32_t *first, float *tex, float *weight, void *stream);
+
+/* One frame of NerfRunner.mesh_vertex_color_from_train_images (nerf_runner.py:
+ * 1446-1458) without the reference's cKDTree. The candidates are the pixels of
+ * a nof_raster_faces z-buffer that nof_texture_hits would take (a face, mask
+ * set, depth >= min_depth), each at its back-projected point in the object
+ * frame (no snap to the face). Per vertex V[j] (f32, widened to f64) the match
+ * is the candidate with the smallest d2 = (dx*dx + dy*dy) + dz*dz in f64, ties
+ * to the lowest pixel index; where sqrt(d2) <= radius its colour is added to
+ * color_sum[j] and 1 to count[j] (plain adds by the vertex's own lane: no
+ * atomics, deterministic). Only the screen window that bounds every candidate
+ * within `radius` is searched, which needs ob_in_cam = inv(cam_in_ob), rigid,
+ * and min_depth > 0. nearest / nearest_dist (either may be NULL) are written
+ * for every vertex on every call: the accepted match's pixel index and
+ * distance, -1 and +inf where there is none. n_vertices == 0 launches nothing. */
+int nof_vertex_color_accumulate(const uint64_t *zbuf, int32_t H, int32_t W, const uint8_t *mask, float min_depth,
+                                const float *colors,      /* [H*W,3] f32: the frame's image */
+                                const double *cam_in_ob, const double *ob_in_cam, const double *K,
+                                const float *V, int64_t n_vertices, double radius,
+                                double *color_sum,        /* [Nv,3] f64, += */
+                                int32_t *count,           /* [Nv] i32, += 1 */
+                                int32_t *nearest,         /* [Nv] i32 or NULL: pixel index of the match, -1 = none */
+                                double *nearest_dist,     /* [Nv] f64 or NULL: its distance, +inf = none */
+                                void *stream);
 
 #ifdef __cplusplus
 }
