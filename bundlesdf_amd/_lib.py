@@ -77,6 +77,10 @@ _SIGNATURES = {
                                      _p], _int),
     "nof_segment_mean": ([_p, _i32, _p, _p, _i32, _p, _p], _int),
     "nof_dbscan": ([_p, _i32, ctypes.c_double, _i32, _p, _p, _p, _p, _p], _int),
+    "nof_marching_cubes_blocks": ([_i32, _i32, _i32, _p], _int),
+    "nof_marching_cubes_count": ([_p, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p], _int),
+    "nof_marching_cubes_emit": ([_p, _i32, _i32, _i32, _f32, _p, _p, _p, _i64, _i64, _p, _p, _p], _int),
+    "nof_mesh_components": ([_p, _i64, _i64, _p, _p, _p], _int),
 }
 
 

@@ -247,10 +247,109 @@ def write_png(path, img):
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
-def marching_cubes(volume, level=0.0):
+def device_tables(device):
+    """The [256,16] uint8 case table nof_marching_cubes_* read, on `device`: per case TRI_COUNT, then the
+    5 x 3 entries of TRI_TABLE, each table edge e as EDGE_CORNER[e] | EDGE_AXIS[e] << 3 (unused slots 0)."""
+    key = str(device)
+    if key not in _DEVICE_TABLES:
+        # the kernels take corner c at offset (c & 1, c >> 1 & 1, c >> 2 & 1): _CORNERS' construction
+        assert all(tuple(_CORNERS[c]) == (c & 1, (c >> 1) & 1, (c >> 2) & 1) for c in range(8))
+        assert TRI_TABLE.shape == (256, 5, 3) and int(TRI_COUNT.max()) <= 5
+        code = EDGE_CORNER | (EDGE_AXIS << 3)
+        t = np.zeros((256, 16), np.uint8)
+        t[:, 0] = TRI_COUNT
+        t[:, 1:] = np.where(TRI_TABLE >= 0, code[np.maximum(TRI_TABLE, 0)], 0).reshape(256, 15)
+        _DEVICE_TABLES[key] = torch.from_numpy(t).to(device)
+    return _DEVICE_TABLES[key]
+
+
+_DEVICE_TABLES = {}
+
+
+def marching_cubes_device(volume, level=0.0):
+    """marching_cubes on the device with the HIP kernels of csrc/mesh.hip (nof_marching_cubes_count /
+    _emit): device tensors (vertices float32 [V,3] in index coordinates, faces int32 [F,3]), equal to
+    marching_cubes(volume, level) bit for bit and in the same order. `volume` [N0,N1,N2]: a device tensor is
+    used where it is (float32 contiguous: no copy), anything else is copied to the current device. One
+    host read: the totals (V, F) with the volume's value range. At most 4 bytes of scratch per grid
+    point (plus 32 per 256 points)."""
+    from . import _lib
+    vol = torch.as_tensor(volume)
+    if not vol.is_cuda:
+        vol = vol.to(torch.device("cuda", torch.cuda.current_device()))
+    vol = vol.float().contiguous()
+    if vol.dim() != 3:
+        raise ValueError(f"marching_cubes_device: volume must be [N0,N1,N2], got {tuple(vol.shape)}")
+    dev = vol.device
+    n0, n1, n2 = (int(n) for n in vol.shape)
+    if max(n0, n1, n2) >= 1 << 31:
+        raise ValueError(f"marching_cubes_device: volume {n0} x {n1} x {n2} is too large")
+    L = _lib.lib()
+    nb = _lib.ctypes.c_int64(0)
+    _lib.check(L.nof_marching_cubes_blocks(n0, n1, n2, _lib.ctypes.byref(nb)), "marching_cubes_blocks")
+    nb = nb.value
+    with torch.cuda.device(dev):
+        tables = device_tables(dev)
+        cells = torch.empty(n0 * n1 * n2, dtype=torch.int32, device=dev)
+        counts = torch.empty((nb, 2), dtype=torch.int32, device=dev)
+        rng = torch.empty((nb, 2), dtype=torch.float32, device=dev)
+        st = _lib.stream_of(vol)
+        _lib.check(L.nof_marching_cubes_count(_lib.ptr(vol), n0, n1, n2, level, _lib.ptr(tables), _lib.ptr(cells),
+                                              _lib.ptr(counts), _lib.ptr(rng), st), "marching_cubes_count")
+        incl = torch.cumsum(counts, 0, dtype=torch.int64)
+        base = (incl - counts).contiguous()
+        stats = torch.cat([incl[-1].double(), rng[:, 0].min().double()[None], rng[:, 1].max().double()[None]]).cpu()
+        V, F, lo, hi = int(stats[0]), int(stats[1]), float(stats[2]), float(stats[3])
+        if not (lo <= level <= hi):
+            raise ValueError("Surface level must be within volume data range.")   # as skimage
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        if V:
+            _lib.check(L.nof_marching_cubes_emit(_lib.ptr(vol), n0, n1, n2, level, _lib.ptr(tables), _lib.ptr(cells),
+                                                 _lib.ptr(base), V, F, _lib.ptr(verts), _lib.ptr(faces), st),
+                       "marching_cubes_emit")
+    return verts, faces
+
+
+def component_labels(faces, n_vertices, device=None):
+    """Connected components of a triangle list on the device (nof_mesh_components): an int32 device tensor
+    [n_vertices], labels[v] = the smallest vertex index of v's component (a vertex in no face labels itself).
+    Ranking the labels gives scipy's connected_components numbering, which numbers components by their
+    first vertex. The kernel does one hook-and-compress sweep; this loop repeats it until a sweep changes
+    nothing, reading one flag per sweep."""
+    from . import _lib
+    f = torch.as_tensor(faces)
+    if device is None:
+        device = f.device if f.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    f = f.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    n = int(n_vertices)
+    if len(f) and (int(f.min()) < 0 or int(f.max()) >= n):
+        raise ValueError(f"component_labels: face corners must be in [0, {n})")
+    L = _lib.lib()
+    with torch.cuda.device(f.device):
+        labels = torch.arange(n, dtype=torch.int32, device=f.device)
+        changed = torch.zeros(1, dtype=torch.int32, device=f.device)
+        if n == 0 or len(f) == 0:
+            return labels
+        for _ in range(n + 1):
+            _lib.check(L.nof_mesh_components(_lib.ptr(f), len(f), n, _lib.ptr(labels), _lib.ptr(changed),
+                                             _lib.stream_of(f)), "mesh_components")
+            if int(changed.item()) == 0:
+                return labels
+    raise RuntimeError(f"component_labels: no fixed point after {n + 1} sweeps")
+
+
+def marching_cubes(volume, level=0.0, backend="torch"):
     """(vertices [V,3] in index coordinates, faces [F,3]) of the `level` set of
     a [N0,N1,N2] volume (torch tensor on any device, or numpy). Faces are
-    oriented with normals towards increasing values (outside of an SDF)."""
+    oriented with normals towards increasing values (outside of an SDF).
+    backend "torch": the tensor ops below, on the volume's device; "hip":
+    marching_cubes_device, the same arrays from the HIP kernels."""
+    if backend == "hip":
+        verts, faces = marching_cubes_device(volume, level)
+        return verts.double().cpu().numpy(), faces.long().cpu().numpy()
+    if backend != "torch":
+        raise ValueError(f"marching_cubes: backend must be 'torch' or 'hip', got {backend!r}")
     vol = torch.as_tensor(volume)
     dev = vol.device
     vol = vol.float()
@@ -299,9 +398,19 @@ def grid_axes(bounds, voxel_size):
     return [np.arange(b[0, d] + 0.5 * voxel_size, b[1, d], voxel_size) for d in range(3)]
 
 
-def trimesh_split(mesh, min_edge=1000):
+def trimesh_split(mesh, min_edge=1000, backend="scipy"):
     """Connected components with at least `min_edge` vertices, as separate meshes
-    (Utils.py:287-298, trimesh.graph.connected_components over mesh.edges)."""
+    (Utils.py:287-298, trimesh.graph.connected_components over mesh.edges).
+    backend "scipy": on the host; "hip": component_labels on the device, the
+    same parts in the same order (components by their lowest vertex)."""
+    if backend == "hip":
+        n = len(mesh.vertices)
+        label = component_labels(mesh.faces, n)
+        roots = torch.nonzero(torch.bincount(label, minlength=n) >= min_edge).view(-1).cpu().numpy()
+        label = label.cpu().numpy()
+        return [mesh.copy().update_vertices(label == c) for c in roots]
+    if backend != "scipy":
+        raise ValueError(f"trimesh_split: backend must be 'scipy' or 'hip', got {backend!r}")
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     n = len(mesh.vertices)
@@ -313,11 +422,14 @@ def trimesh_split(mesh, min_edge=1000):
     return out
 
 
-def largest_component(mesh, min_edge=100):
+def largest_component(mesh, min_edge=100, backend="scipy"):
     """bundlesdf.py:748-759: merge vertices, split, keep the component with the
-    most vertices (None when every component is below `min_edge`)."""
+    most vertices (None when every component is below `min_edge`). backend as
+    trimesh_split's."""
+    if backend not in ("scipy", "hip"):
+        raise ValueError(f"largest_component: backend must be 'scipy' or 'hip', got {backend!r}")
     mesh.merge_vertices()
-    parts = trimesh_split(mesh, min_edge=min_edge)
+    parts = trimesh_split(mesh, min_edge=min_edge, backend=backend)
     return max(parts, key=lambda m: len(m.vertices)) if parts else None
 
 

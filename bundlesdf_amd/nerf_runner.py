@@ -676,19 +676,27 @@ class NerfRunner:
         return mesh
 
     @torch.no_grad()
-    def extract_mesh(self, level=None, voxel_size=0.003, isolevel=0.0, return_sigma=False):
+    def extract_mesh(self, level=None, voxel_size=0.003, isolevel=0.0, return_sigma=False, mesher=None):
         """nerf_runner.py:1349-1408: sdf on the dense grid of voxel centres over
         cfg['bounding_box'] (voxel_size in metres, scaled by sc_factor), points in
         empty octree voxels at the ray-tracing level read 1.0, marching cubes at
         `isolevel`, vertices mapped back to network space. Returns a Mesh
-        (.vertices, .faces, .export) — trimesh is not available here."""
+        (.vertices, .faces, .export) — trimesh is not available here.
+        mesher: "torch" (mesh.marching_cubes' tensor ops) or "hip" (the kernels of
+        csrc/mesh.hip on query_sdf's device volume: no host copy of the volume, one
+        host read for the totals; the same mesh); None reads cfg['mesh_extractor']
+        (not a reference key), "torch" when absent."""
         from .mesh import Mesh, grid_axes, marching_cubes
+        if mesher is None:
+            mesher = self.cfg.get("mesh_extractor", "torch")
+        if mesher not in ("torch", "hip"):
+            raise ValueError(f"extract_mesh: mesher must be 'torch' or 'hip', got {mesher!r}")
         voxel_size *= self.cfg["sc_factor"]
         tx, ty, tz = grid_axes(self.cfg["bounding_box"], voxel_size)
         occ = self._occ_trace_level() if self.octree_m is not None else None
         sdf = self.trainer.query_sdf(axes=(tx, ty, tz), occ=occ).reshape(len(tx), len(ty), len(tz))
         try:
-            vertices, faces = marching_cubes(sdf, isolevel)
+            vertices, faces = marching_cubes(sdf, isolevel, backend=mesher)
         except Exception as e:   # the reference logs and returns None
             logging.info(f"ERROR Marching Cubes {e}")
             return None

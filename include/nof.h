@@ -630,6 +630,50 @@ int nof_vertex_color_accumulate(const uint64_t *zbuf, int32_t H, int32_t W, cons
                                 double *nearest_dist,     /* [Nv] f64 or NULL: its distance, +inf = none */
                                 void *stream);
 
+/* ------------------------------------------------------------------ group 6
+ * Mesh extraction on the device: the marching cubes of
+ * NerfRunner.extract_mesh (nerf_runner.py:1349-1408, skimage there) and the
+ * connected components of trimesh_split / largest_component (Utils.py:287-298,
+ * bundlesdf.py:748-759). Both give what bundlesdf_amd/mesh.py's torch / scipy
+ * code gives, bit for bit and in the same order.
+ */
+
+/* Shape check and launch geometry of the two calls below: volume [n0,n1,n2] with every n >= 2 and
+ * n0 n1 n2 3 < 2^31 (NOF_EINVAL otherwise, nothing else is looked at); *n_blocks = blocks of 256
+ * consecutive grid points (row-major, n2 fastest) = rows of block_counts / block_range / block_base. */
+int nof_marching_cubes_blocks(int32_t n0, int32_t n1, int32_t n2, int64_t *n_blocks);
+
+/* Counting pass. volume [n0,n1,n2] f32 contiguous; inside = value < level. tables [256,16] u8 from
+ * bundlesdf_amd/mesh.py (device_tables): per case its triangle count, then 5 x 3 codes
+ * corner | axis << 3 of the table edges (corner c = offset (c & 1, c >> 1 & 1, c >> 2 & 1) along
+ * (n0, n1, n2), the case's bit c). Outputs: cells [points] u32, one word per grid point (its owned-edge
+ * crossings, its cell's case and both block-local offsets: 4 bytes per grid point, the pass's only
+ * volume-sized temporary); block_counts [n_blocks,2] i32 vertices and faces per block; block_range
+ * [n_blocks,2] f32 smallest and largest value of the block. The shape is validated before anything
+ * else, every argument before the launch. */
+int nof_marching_cubes_count(const float *volume, int32_t n0, int32_t n1, int32_t n2, float level, const uint8_t *tables,
+                             uint32_t *cells, int32_t *block_counts, float *block_range, void *stream);
+
+/* Emit pass on the same volume / level / tables / cells. block_base [n_blocks,2] i64: the exclusive
+ * prefix sums of block_counts' two columns; n_vertices, n_faces their totals. vertices [n_vertices,3]
+ * f32 in index coordinates: the vertex of grid edge (q, axis a), q + clamp((level - v(q)) / (v(q + e_a)
+ * - v(q)), 0, 1) e_a in f32 with an IEEE division, at position rank of linear(q) 3 + a among the crossed
+ * edges. faces [n_faces,3] i32: cells in row-major order, a cell's triangles in table order, corners
+ * [0, 2, 1] of the table row. Nothing is written past either total. */
+int nof_marching_cubes_emit(const float *volume, int32_t n0, int32_t n1, int32_t n2, float level, const uint8_t *tables,
+                            const uint32_t *cells, const int64_t *block_base, int64_t n_vertices, int64_t n_faces,
+                            float *vertices, int32_t *faces, void *stream);
+
+/* One sweep of connected-component labelling over a triangle list: faces [n_faces,3] i32 with
+ * corners in [0, n_vertices) (other faces are skipped), labels [n_vertices] i32 with labels[v] <= v
+ * (the caller starts from labels[v] = v). For every face the larger of its corners' roots are hooked
+ * under the smallest (atomicMin), then every vertex is pointed at its root. *changed (device int,
+ * cleared by the call) is set when a hook lowered a label; the caller repeats the call until it stays
+ * 0 — every sweep that sets it lowers at least one label, so n_vertices + 1 sweeps bound the loop —
+ * and then labels[v] is the smallest vertex index of v's component (a vertex in no face: itself). */
+int nof_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_vertices, int32_t *labels, int32_t *changed,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
