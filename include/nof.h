@@ -674,6 +674,38 @@ int nof_marching_cubes_emit(const float *volume, int32_t n0, int32_t n1, int32_t
 int nof_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_vertices, int32_t *labels, int32_t *changed,
                         void *stream);
 
+/* ------------------------------------------------------------------ group 7
+ * Pose and mesh evaluation (benchmark_ho3d.py:18-139 with Utils.py:82-103,
+ * 268-273): the nearest-neighbour search behind ADD-S, the chamfer distance and
+ * the point-to-point ICP before it (cKDTree and open3d there).
+ */
+
+/* Exact nearest neighbour of every query in a cloud of n points held in the grid
+ * nof_point_grid_build made of it (cell_start, cell_points, cell_ids — required
+ * here — and the same origin / dims / cell; at most 2^26 cells). queries [Q,3]
+ * f64; xforms [B,4,4] f64 row-major or NULL (then B must be 1: the identity),
+ * B <= 65535. For transform a the query is q = ((T[a][0] x + T[a][1] y) + T[a][2]
+ * z) + T[a][3] per row, d2 = (dx dx + dy dy) + dz dz with dx = c_x - q_x, all in
+ * f64 without contraction. index [B,Q] i32: the lowest input index among the
+ * points of smallest d2; dist [B,Q] f64 = sqrt(d2). max_dist > 0: a query whose
+ * dist is above it gets index -1 and dist +inf (max_dist <= 0: no limit).
+ * Queries may lie anywhere, also outside the grid's box. Q == 0 or B == 0 returns
+ * 0 at once; n == 0 with queries is NOF_EINVAL. */
+int nof_nearest_points(const double *queries, int32_t Q, const double *xforms, int32_t B, const int32_t *cell_start,
+                       const double *cell_points, const int32_t *cell_ids, int32_t n, const double *origin,
+                       const int32_t *dims, double cell, double max_dist, int32_t *index, double *dist, void *stream);
+
+/* The sums of one point-to-point registration step over the pairs (p'_i,
+ * q_i = target[index[i]]) with 0 <= index[i] < m, where p' is source [n,3] f64
+ * moved by xform [4,4] f64 row-major (device memory; NULL = identity) in the
+ * operation order above: sums [17] f64 (device) = count, sum p' (3), sum q (3),
+ * sum p' q^T (9, row-major: p' component first), sum dist[i]^2. Per-block partial
+ * sums go to workspace (nof_nearest_workspace_bytes(n) bytes) and one block adds
+ * them in block order: no floating-point atomics, the same bits on every run. */
+size_t nof_nearest_workspace_bytes(int32_t n);
+int nof_correspondence_moments(const double *source, int32_t n, const double *xform, const double *target, int32_t m,
+                               const int32_t *index, const double *dist, double *sums, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
