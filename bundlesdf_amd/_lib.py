@@ -81,6 +81,11 @@ _SIGNATURES = {
     "nof_marching_cubes_count": ([_p, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p], _int),
     "nof_marching_cubes_emit": ([_p, _i32, _i32, _i32, _f32, _p, _p, _p, _i64, _i64, _p, _p, _p], _int),
     "nof_mesh_components": ([_p, _i64, _i64, _p, _p, _p], _int),
+    "nof_mesh_laplacian_step": ([_p, _p, _p, _i64, ctypes.c_double, _p, _p], _int),
+    "nof_mesh_volume_workspace_bytes": ([_i64], ctypes.c_size_t),
+    "nof_mesh_volume": ([_p, _p, _i64, _p, _p, _p], _int),
+    "nof_mesh_scale_to_volume": ([_p, _i64, _p, _p, _p, _p], _int),
+    "nof_mesh_vertex_normals": ([_p, _p, _p, _p, _i64, _p, _p], _int),
     "nof_nearest_points": ([_p, _i32, _p, _i32, _p, _p, _p, _i32, _p, _p, ctypes.c_double, ctypes.c_double, _p, _p,
                             _p], _int),
     "nof_nearest_workspace_bytes": ([_i32], ctypes.c_size_t),

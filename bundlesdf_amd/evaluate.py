@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .handoff import PointCloud
-from .mesh import trimesh_split
+from .mesh import trimesh_clean, trimesh_split
 
 __all__ = ["PointGrid", "nearest", "add_err", "adi_err", "compute_auc", "chamfer_distance_between_clouds_mutual",
            "sample_surface", "icp_point_to_point", "correspondence_moments", "align_first_frame", "evaluate_poses",
@@ -328,15 +328,8 @@ def evaluate_poses(pred_poses, gt_poses, model_pts):
 
 
 def _clean(mesh):
-    """Utils.py:278-284 (trimesh_clean) with what Mesh has: weld, drop faces that repeat a vertex index,
-    drop duplicate faces, drop vertices no face uses."""
-    mesh.merge_vertices()
-    f = mesh.faces
-    mesh.faces = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
-    mesh.remove_duplicate_faces()
-    used = np.zeros(len(mesh.vertices), bool)
-    used[mesh.faces.reshape(-1)] = True
-    return mesh.update_vertices(used)
+    """Utils.py:278-284: mesh.trimesh_clean (weld, degenerate and duplicate faces, unused vertices)."""
+    return trimesh_clean(mesh)
 
 
 def evaluate_mesh(pred_mesh, gt_pts, voxel=0.005, n_samples=99999, icp_thres=0.02, min_edge=1000, seed=0,

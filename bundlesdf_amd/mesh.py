@@ -168,6 +168,41 @@ class Mesh:
         self._take_vertex_rows(mask)
         return self
 
+    def compute_vertex_normals(self, backend="hip"):
+        """Set and return vertex_normals [V,3] f64 from the geometry: per vertex the unnormalised
+        (v1 - v0) x (v2 - v0) of its faces (area weights) added in ascending face index, divided by
+        the sum's length; a zero sum gives (0, 0, 0). backend "hip": nof_mesh_vertex_normals, a gather
+        over the vertex -> face CSR; "scipy": the same sums in numpy on the host."""
+        _check_backend("compute_vertex_normals", backend)
+        V = len(self.vertices)
+        dev = _device() if backend == "hip" else torch.device("cpu")
+        faces = _checked_faces("compute_vertex_normals", self.faces, V, dev)
+        row_start, face_ids = vertex_faces(faces, V, device=dev)
+        if backend == "hip":
+            from . import _lib
+            v = torch.from_numpy(np.array(self.vertices, np.float64)).to(dev)
+            f32 = faces.to(torch.int32).contiguous()
+            out = torch.empty_like(v)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().nof_mesh_vertex_normals(_lib.ptr(v), _lib.ptr(f32), _lib.ptr(row_start),
+                                                              _lib.ptr(face_ids), V, _lib.ptr(out), _lib.stream_of(v)),
+                           "mesh_vertex_normals")
+            self.vertex_normals = out.cpu().numpy()
+            return self.vertex_normals
+        v, f = self.vertices, faces.numpy()
+        t = v[f]
+        fn = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]).reshape(-1, 3)
+        rs, ids = row_start.numpy().astype(np.int64), face_ids.numpy()
+        s = np.zeros((V, 3))
+        deg = np.diff(rs)
+        for r in range(int(deg.max()) if V else 0):     # the r-th face of every row that has one: ascending order
+            rows = np.flatnonzero(deg > r)
+            s[rows] = s[rows] + fn[ids[rs[rows] + r]]
+        n = np.sqrt((s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1]) + s[:, 2] * s[:, 2])
+        ok = n > 0
+        self.vertex_normals = np.where(ok[:, None], s / np.where(ok, n, 1.0)[:, None], 0.0)
+        return self.vertex_normals
+
     def export(self, path):
         if path.endswith(".obj"):
             import os
@@ -438,3 +473,228 @@ def mesh_to_real_world(mesh, pose_offset, translation, sc_factor):
     mesh.vertices = mesh.vertices / sc_factor - np.asarray(translation, np.float64).reshape(1, 3)
     mesh.apply_transform(pose_offset)
     return mesh
+
+
+def trimesh_clean(mesh):
+    """Utils.py:278-284 (trimesh_clean) with what Mesh has: weld, drop faces that repeat a vertex index,
+    drop duplicate faces, drop vertices no face uses. In place; returns the mesh."""
+    mesh.merge_vertices()
+    f = mesh.faces
+    mesh.faces = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
+    mesh.remove_duplicate_faces()
+    used = np.zeros(len(mesh.vertices), bool)
+    used[mesh.faces.reshape(-1)] = True
+    return mesh.update_vertices(used)
+
+
+_VOLUME_ERROR = "volume_constraint needs a closed, outward-oriented mesh"
+
+
+def _check_backend(what, backend):
+    if backend not in ("scipy", "hip"):
+        raise ValueError(f"{what}: backend must be 'scipy' or 'hip', got {backend!r}")
+
+
+def _device(device=None):
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _checked_faces(what, faces, n_vertices, device):
+    """faces as an int64 [F,3] tensor on `device`; ValueError for a corner outside [0, n_vertices)."""
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.array(faces, np.int64))   # a writable copy
+    f = f.to(device=device, dtype=torch.int64).reshape(-1, 3)
+    n = int(n_vertices)
+    if n < 0 or n * 3 >= 1 << 31 or len(f) * 3 >= 1 << 31:
+        raise ValueError(f"{what}: {n} vertices, {len(f)} faces: both times 3 must be below 2^31")
+    if len(f) and (int(f.min()) < 0 or int(f.max()) >= n):
+        raise ValueError(f"{what}: face corners must be in [0, {n})")
+    return f
+
+
+def _csr(rows, vals, n_rows, n_vals):
+    """CSR (row_start [n_rows+1] int32, cols int32) of the distinct (row, val) pairs, vals ascending
+    within a row: one sort of the keys row * n_vals + val and unique_consecutive, on the pairs' device."""
+    key = torch.unique_consecutive(torch.sort(rows * max(int(n_vals), 1) + vals).values)
+    r = torch.div(key, max(int(n_vals), 1), rounding_mode="floor")
+    row_start = torch.zeros(int(n_rows) + 1, dtype=torch.int64, device=key.device)
+    row_start[1:] = torch.cumsum(torch.bincount(r, minlength=int(n_rows)), 0)
+    return row_start.to(torch.int32), (key - r * max(int(n_vals), 1)).to(torch.int32)
+
+
+def vertex_adjacency(faces, n_vertices, device=None):
+    """(row_start [V+1], cols [E]) int32 tensors on `device` (default: the faces' device when they are a
+    device tensor, else the current HIP device): row v holds the distinct vertices that share a face
+    edge with v, ascending. An edge shared by several faces counts once; the self-edge of a degenerate
+    face (a, a, b) is dropped; a corner outside [0, n_vertices) raises ValueError."""
+    if device is None and torch.is_tensor(faces) and faces.is_cuda:
+        device = faces.device
+    f = _checked_faces("vertex_adjacency", faces, n_vertices, _device(device))
+    a = torch.cat([f[:, [0, 1, 2]].reshape(-1), f[:, [1, 2, 0]].reshape(-1)])   # every face edge, both directions
+    b = torch.cat([f[:, [1, 2, 0]].reshape(-1), f[:, [0, 1, 2]].reshape(-1)])
+    keep = a != b
+    return _csr(a[keep], b[keep], n_vertices, n_vertices)
+
+
+def vertex_faces(faces, n_vertices, device=None):
+    """The vertex -> face CSR (row_start [V+1], face_ids) int32 on `device`, by vertex_adjacency's routine
+    keyed (vertex, face): the faces of v, each once, in ascending face index."""
+    if device is None and torch.is_tensor(faces) and faces.is_cuda:
+        device = faces.device
+    f = _checked_faces("vertex_faces", faces, n_vertices, _device(device))
+    ids = torch.arange(len(f), dtype=torch.int64, device=f.device)[:, None].expand(-1, 3).reshape(-1)
+    return _csr(f.reshape(-1), ids, n_vertices, len(f))
+
+
+def _volume_host(vertices, faces):
+    t = np.asarray(vertices, np.float64)[np.asarray(faces, np.int64).reshape(-1, 3)]
+    return float(np.sum(np.sum(t[:, 0] * np.cross(t[:, 1], t[:, 2]).reshape(-1, 3), axis=1)) / 6.0)
+
+
+def mesh_volume(mesh_or_vertices, faces=None, backend="hip"):
+    """Signed volume sum_f v0 . (v1 x v2) / 6 of a triangle mesh (a Mesh, or vertices with faces), as a
+    float: positive for a closed mesh whose faces are oriented outwards. backend "hip":
+    nof_mesh_volume (f64, per-block partial sums added in block order: the same bits on every run);
+    "scipy": numpy on the host."""
+    _check_backend("mesh_volume", backend)
+    if faces is None:
+        mesh_or_vertices, faces = mesh_or_vertices.vertices, mesh_or_vertices.faces
+    vertices = np.array(mesh_or_vertices, np.float64).reshape(-1, 3)
+    if backend == "scipy":
+        f = _checked_faces("mesh_volume", faces, len(vertices), torch.device("cpu")).numpy()
+        return _volume_host(vertices, f)
+    from . import _lib
+    dev = _device()
+    f = _checked_faces("mesh_volume", faces, len(vertices), dev).to(torch.int32).contiguous()
+    v = torch.from_numpy(vertices).to(dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(L.nof_mesh_volume_workspace_bytes(len(f))), dtype=torch.uint8, device=dev)
+        _lib.check(L.nof_mesh_volume(_lib.ptr(v), _lib.ptr(f), len(f), _lib.ptr(out), _lib.ptr(ws), _lib.stream_of(v)),
+                   "mesh_volume")
+    return float(out.item())
+
+
+def _smooth_hip(vertices, faces, factors, volume_constraint):
+    """The filter loop on the device, all of it enqueued on one stream: per factor one
+    nof_mesh_laplacian_step, with the constraint followed by nof_mesh_volume and nof_mesh_scale_to_volume
+    towards the initial volume. One host read at the end: the vertices with the initial volume and the flag."""
+    from . import _lib
+    dev = _device()
+    V = len(vertices)
+    f = _checked_faces("filter", faces, V, dev)
+    row_start, cols = vertex_adjacency(f, V, device=dev)
+    f32 = f.to(torch.int32).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        a = torch.from_numpy(np.array(vertices, np.float64)).to(dev)
+        b = torch.empty_like(a)
+        vol0, vol = torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(L.nof_mesh_volume_workspace_bytes(len(f32))), dtype=torch.uint8, device=dev)
+        st = _lib.stream_of(a)
+        if volume_constraint:
+            _lib.check(L.nof_mesh_volume(_lib.ptr(a), _lib.ptr(f32), len(f32), _lib.ptr(vol0), _lib.ptr(ws), st),
+                       "mesh_volume")
+        for factor in factors:
+            _lib.check(L.nof_mesh_laplacian_step(_lib.ptr(a), _lib.ptr(row_start), _lib.ptr(cols), V, float(factor),
+                                                 _lib.ptr(b), st), "mesh_laplacian_step")
+            a, b = b, a
+            if volume_constraint:
+                _lib.check(L.nof_mesh_volume(_lib.ptr(a), _lib.ptr(f32), len(f32), _lib.ptr(vol), _lib.ptr(ws), st),
+                           "mesh_volume")
+                _lib.check(L.nof_mesh_scale_to_volume(_lib.ptr(a), V, _lib.ptr(vol0), _lib.ptr(vol), _lib.ptr(flag),
+                                                      st), "mesh_scale_to_volume")
+        out = torch.cat([a.reshape(-1), vol0, flag.double()]).cpu().numpy()
+    if volume_constraint and (out[-1] != 0 or not out[-2] > 0):
+        raise ValueError(_VOLUME_ERROR)
+    return out[:-2].reshape(V, 3)
+
+
+def _smooth_host(vertices, faces, factors, volume_constraint):
+    """The same definition on the host: a scipy.sparse CSR operator with 1 / degree in every stored entry
+    of the same adjacency (a row product adds its entries in stored order), volume by numpy."""
+    from scipy.sparse import csr_matrix
+    V = len(vertices)
+    f = _checked_faces("filter", faces, V, torch.device("cpu"))
+    row_start, cols = (t.numpy() for t in vertex_adjacency(f, V, device="cpu"))
+    f = f.numpy()
+    deg = np.diff(row_start)
+    w = np.repeat(1.0 / np.maximum(deg, 1), deg)
+    op = csr_matrix((w, cols, row_start), shape=(V, V))
+    isolated = (deg == 0)[:, None]
+    v = np.array(vertices, np.float64)
+    vol0 = _volume_host(v, f) if volume_constraint else 0.0
+    if volume_constraint and not vol0 > 0:
+        raise ValueError(_VOLUME_ERROR)
+    for factor in factors:
+        v = np.where(isolated, v, v + float(factor) * (op @ v - v))
+        if volume_constraint:
+            r = vol0 / _volume_host(v, f)
+            if not (r > 0 and np.isfinite(r)):
+                raise ValueError(_VOLUME_ERROR)
+            v = v * np.cbrt(r)
+    return v
+
+
+def _smooth(what, mesh, factors, volume_constraint, backend):
+    _check_backend(what, backend)
+    if not all(np.isfinite(x) for x in factors):
+        raise ValueError(f"{what}: lamb / nu must be finite")
+    if not factors or len(mesh.vertices) == 0:
+        return mesh
+    run = _smooth_hip if backend == "hip" else _smooth_host
+    mesh.vertices = run(mesh.vertices, mesh.faces, factors, volume_constraint)   # raises before assigning
+    mesh.vertex_normals = None      # they described the old surface
+    return mesh
+
+
+def filter_laplacian(mesh, lamb=0.5, iterations=10, volume_constraint=True, backend="hip"):
+    """trimesh.smoothing.filter_laplacian(mesh, lamb, iterations, implicit_time_integration=False,
+    volume_constraint) with the default (uniform-weight) operator. Per iteration every vertex moves by
+    lamb of the way to the mean of its neighbours (vertex_adjacency), all vertices at once:
+    v + lamb (m - v), m = ((w v[j0] + w v[j1]) + ...), w = 1 / degree; a vertex without neighbours stays
+    (trimesh pulls it towards the origin). With volume_constraint each iteration is followed by a
+    rescale about the origin by cbrt(initial volume / volume); a mesh whose initial volume is not
+    positive, or whose volume stops being so, raises ValueError and is left untouched. In place:
+    vertices change, vertex_normals become None, faces and the other attributes stay. iterations == 0
+    is the identity. backend "hip": the device loop of _smooth_hip (nof_mesh_laplacian_step, nof_mesh_volume,
+    nof_mesh_scale_to_volume; one host read); "scipy": the same definition on the host."""
+    return _smooth("filter_laplacian", mesh, [float(lamb)] * int(iterations), volume_constraint, backend)
+
+
+def filter_taubin(mesh, lamb=0.5, nu=0.5, iterations=10, backend="hip"):
+    """Taubin's filter with trimesh.smoothing.filter_taubin's signature and defaults: filter_laplacian's
+    step with factor lamb in iteration k = 0, 2, 4, ... and factor -nu in k = 1, 3, 5, ... (the shrinking
+    step and the inflating step alternate), no volume constraint. This is the definition here; parity
+    with trimesh is not pinned by a test. In place, as filter_laplacian."""
+    factors = [float(lamb) if k % 2 == 0 else -float(nu) for k in range(int(iterations))]
+    return _smooth("filter_taubin", mesh, factors, False, backend)
+
+
+def postprocess_mesh(mesh, translation, sc_factor, out_dir=None, min_edge=1000, lamb=0.5, iterations=3, backend="hip"):
+    """run_custom.py:158-188 for a normalised-space Mesh -> {"real_scale", "biggest_component", "smoothed"}.
+
+    On a copy: vertices / sc_factor - translation (the inverse of the normalisation); trimesh_split(min_edge,
+    backend) and the component with the most vertices (ValueError when there is none); trimesh_clean;
+    filter_laplacian(lamb, iterations, volume_constraint=True, backend) on a copy of that, then
+    compute_vertex_normals(backend). With out_dir the three meshes are also written there under the
+    reference's names: mesh_real_scale.obj, mesh_biggest_component.obj, mesh_biggest_component_smoothed.obj."""
+    _check_backend("postprocess_mesh", backend)
+    real = mesh.copy()
+    real.vertices = real.vertices / sc_factor - np.asarray(translation, np.float64).reshape(1, 3)
+    parts = trimesh_split(real, min_edge=min_edge, backend=backend)
+    if not parts:
+        raise ValueError(f"postprocess_mesh: no component with at least {min_edge} vertices")
+    biggest = trimesh_clean(max(parts, key=lambda m: len(m.vertices)))
+    smoothed = filter_laplacian(biggest.copy(), lamb=lamb, iterations=iterations, volume_constraint=True,
+                                backend=backend)
+    smoothed.compute_vertex_normals(backend=backend)
+    out = {"real_scale": real, "biggest_component": biggest, "smoothed": smoothed}
+    if out_dir is not None:
+        import os
+        os.makedirs(out_dir, exist_ok=True)
+        for key, name in (("real_scale", "mesh_real_scale.obj"), ("biggest_component", "mesh_biggest_component.obj"),
+                          ("smoothed", "mesh_biggest_component_smoothed.obj")):
+            out[key].export(os.path.join(out_dir, name))
+    return out

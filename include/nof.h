@@ -674,6 +674,45 @@ int nof_marching_cubes_emit(const float *volume, int32_t n0, int32_t n1, int32_t
 int nof_mesh_components(const int32_t *faces, int64_t n_faces, int64_t n_vertices, int32_t *labels, int32_t *changed,
                         void *stream);
 
+/* Mesh smoothing: the tail of the reference's postprocess_mesh (run_custom.py:158-188,
+ * trimesh.smoothing.filter_laplacian there). All of it is f64 in the stated operation order, without
+ * contraction and without floating-point atomics, and no call waits for the host.
+ *
+ * One explicit (Jacobi) Laplacian step from v_in to v_out, both [V,3] f64 and distinct buffers. The
+ * adjacency is CSR: row_start [V+1] i32, cols i32 (bundlesdf_amd/mesh.py vertex_adjacency: the distinct
+ * neighbours of a vertex, ascending). For vertex i of degree d = row_start[i+1] - row_start[i] > 0, per
+ * component: w = 1.0 / d, m = ((w v[j0] + w v[j1]) + w v[j2]) + ... over the row in stored order,
+ * v_out[i] = v[i] + factor (m - v[i]). d == 0: v_out[i] = v[i] (trimesh's operator has a zero row there
+ * and pulls the vertex towards the origin). A column outside [0, V) stands for vertex i itself. factor
+ * must be finite; lamb for a Laplacian step, -nu for the odd steps of Taubin's filter. */
+int nof_mesh_laplacian_step(const double *v_in, const int32_t *row_start, const int32_t *cols, int64_t V, double factor,
+                            double *v_out, void *stream);
+
+/* Signed volume of a triangle mesh, *volume_out (device f64) = (sum_f v0 . (v1 x v2)) / 6 with
+ * c = (y1 z2 - z1 y2, z1 x2 - x1 z2, x1 y2 - y1 x2) and term = (x0 cx + y0 cy) + z0 cz. vertices [*,3]
+ * f64, faces [F,3] i32 with every corner a valid vertex index (not checked: there is no vertex count).
+ * A fixed thread-to-face assignment, a butterfly over the wave, the four waves added in order, one
+ * partial per block in workspace (nof_mesh_volume_workspace_bytes(F) bytes, at most 1024 blocks), and
+ * one block adds the partials in block order: the same bits on every run. F == 0 gives 0. */
+size_t nof_mesh_volume_workspace_bytes(int64_t F);
+int nof_mesh_volume(const double *vertices, const int32_t *faces, int64_t F, double *volume_out, void *workspace,
+                    void *stream);
+
+/* trimesh's volume constraint: every coordinate of vertices [V,3] f64 times s = cbrt(*vol_target /
+ * *vol_now), about the origin. Both volumes are device f64. When the ratio is not a positive finite
+ * number the vertices are left as they are and *flag (device i32, never cleared here) is set to 1. */
+int nof_mesh_scale_to_volume(double *vertices, int64_t V, const double *vol_target, const double *vol_now, int32_t *flag,
+                             void *stream);
+
+/* Area-weighted vertex normals from the geometry: normals_out [V,3] f64. face_row_start [V+1] i32 /
+ * face_ids i32 is the vertex -> face CSR (the faces of a vertex, each once, in ascending face index).
+ * Per vertex s = 0, then s = s + (v1 - v0) x (v2 - v0) face by face in that order, with u = v1 - v0,
+ * w = v2 - v0 and the cross product (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx); len = sqrt((sx sx +
+ * sy sy) + sz sz), normal = s / len (IEEE division), (0,0,0) when len is not > 0. A gather: no atomics.
+ * A face with a corner outside [0, V) is skipped. */
+int nof_mesh_vertex_normals(const double *vertices, const int32_t *faces, const int32_t *face_row_start,
+                            const int32_t *face_ids, int64_t V, double *normals_out, void *stream);
+
 /* ------------------------------------------------------------------ group 7
  * Pose and mesh evaluation (benchmark_ho3d.py:18-139 with Utils.py:82-103,
  * 268-273): the nearest-neighbour search behind ADD-S, the chamfer distance and
