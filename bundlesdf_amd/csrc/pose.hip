@@ -277,7 +277,8 @@ __global__ void k_zero_f32(float *__restrict__ p, int n) {
 
 extern "C" int nof_pose_backward(const float *ray_grad, const float *rays, int32_t R, const float *jac, int32_t F,
                                  float *fg, float *grad_pose, void *stream) {
-    if (!ray_grad || !rays || !jac || !fg || !grad_pose || R < 0 || F <= 0 || F > 1024)
+    // an empty batch has no per-ray buffers (a zero-size allocation is a null pointer): the pose gradient is zero
+    if ((R > 0 && (!ray_grad || !rays)) || !jac || !fg || !grad_pose || R < 0 || F <= 0 || F > 1024)
         return nof::set_error(NOF_EINVAL, "pose_backward: bad arguments (F <= 1024)");
     hipStream_t st = (hipStream_t)stream;
     // fg is zero on entry and left zero (k_pose_grad clears what it consumed): no zeroing launch

@@ -425,7 +425,7 @@ int nof_step_prologue(const nof_schedule_desc *sched, int32_t *step, nof_step_pa
 
 /* Pose gradient: fg[F,12] (scratch: zero on entry, left zero) = per-frame sum of
  * ray_grad [R,12] over the rays' frame ids (rays [R,12], column 8); grad_pose [F,6]
- * += jac^T fg. F <= 1024. */
+ * += jac^T fg. F <= 1024. R = 0 (an empty batch: ray_grad / rays may be null) adds nothing. */
 int nof_pose_backward(const float *ray_grad, const float *rays, int32_t R, const float *jac, int32_t F, float *fg,
                       float *grad_pose, void *stream);
 

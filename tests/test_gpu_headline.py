@@ -1,8 +1,14 @@
-"""The production step at BASELINE's headline size: 64 frames x 2048
+"""The training step at BASELINE's headline size: 64 frames x 2048
 rays = 131,072 rays per step, 192 samples/ray, L=16 (finest 128, 2^22), amp — the shape
 bench.py times, with every size-selected branch the library takes only there (the
 16-flags-per-thread tile compaction from 262,144 tiles, the quad-mirror encode from 32 K
 rays, 8 scatter levels per wave from 32 K rays, the block-reduced MLP flush).
+
+Which kernel instances run: the eager steps here (_eager, the oracle subset test) call
+step(debug=True), i.e. the DBG = true instances of k_encode / k_colour — the colour net on every
+tile, tile flags 1 and 3 only, no sigma-only backward record; only the graph-replay test (and its
+eager twin, debug=False) runs the DBG = false instances bench.py times. Those are held against
+the oracle at parity size in test_gpu_production.py.
 
 The oracle cannot run this size in test time, so the checks are size-independent
 properties of the same step:
@@ -110,9 +116,10 @@ def test_headline_quad_mirror_fork_equals_inline(headline):
 
 
 def test_headline_step_subset_matches_oracle(headline):
-    """The 131,072-ray production step (quad-mirror encode, 16-flag compaction, k_colour at headline
-    occupancy, 8 scatter levels per wave) with injected stratification draws, checked against the
-    oracle:
+    """The 131,072-ray step (quad-mirror encode, 16-flag compaction, k_colour at headline
+    occupancy, 8 scatter levels per wave) run with debug=True — the debug instances of k_encode /
+    k_colour, whose per-sample records the check needs — with injected stratification draws, checked
+    against the oracle:
       * forward: rays are independent in the forward, so 512 rays spread over the 64 frames are
         compared with the oracle's amp step on those rays alone — z (2e-6), validity (exact), the
         fp16 raw outputs and rgb (the amp forward tolerances of test_gpu_step);
