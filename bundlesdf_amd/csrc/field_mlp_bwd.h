@@ -1,8 +1,9 @@
+// Included in place by field_step.hip, inside namespace nof, after bwd_entry (training only).
 // The MLP backward kernels of the fused field step: k_mlp_bwd (fp32 / generic) and k_mlp_bwd_tr
-// (amp, LDS transposes), with their weight-gradient flushes. Not a standalone header: field_step.hip
-// includes it inside namespace nof, after the forward kernels whose helpers (FieldArgs, the MFMA
-// fragment helpers, the tile records, bwd_entry) it uses.
+// (amp, LDS transposes), with their weight-gradient flushes. Not a standalone header: beyond
+// field_core.h it uses the step's tile records, stage_block and bwd_entry, defined above its include line.
 #pragma once
+#include "field_core.h"
 
 // ---------------------------------------------- kernel 3: MLP backward + dW
 // Persistent waves (one per SIMD) over the tiles k_encode flagged (k_compact's
@@ -158,9 +159,9 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(WAVES,
     const int n = lane & 31, h = lane >> 5;
     typedef typename FragT<TM>::T Frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    stage_mlp<TM>(a, smem);
+    stage_block<TM, N_FRAGS, 0>(a, smem);
     const TM *s_fr = reinterpret_cast<const TM *>(smem);
-    const float *s_b = reinterpret_cast<const float *>(smem + N_FRAGS * 64 * 8 * sizeof(TM));
+    const float *s_b = staged_bias<TM, N_FRAGS>(smem);
     const LdsW<TM> W{s_fr};
     const float lscale = *a.loss_scale;
     const int n_c = __builtin_amdgcn_readfirstlane(a.n_tiles[0]);
@@ -713,11 +714,11 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = lane & 31, h = lane >> 5;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (PASS == 0) stage_mlp<TM>(a, smem);
+    if constexpr (PASS == 0) stage_block<TM, N_FRAGS, 0>(a, smem);
     else stage_sigma_bwd(a, smem);
     const TM *s_fr = reinterpret_cast<const TM *>(smem);
-    const float *s_b = reinterpret_cast<const float *>(smem + (PASS == 0 ? N_FRAGS : S1_NFR) * 64 * 8 * sizeof(TM));
-    float *s_ff = const_cast<float *>(s_b) + 5 * 64 + 4 * wave;   // PASS 0 (FF) only
+    const float *s_b = staged_bias<TM, (PASS == 0 ? N_FRAGS : S1_NFR)>(smem);
+    float *s_ff = const_cast<float *>(s_b) + BIAS_WORDS + 4 * wave;   // PASS 0 (FF) only
     char *img = smem + bwd_tr_img_base(PASS, WPB) + (size_t)wave * (PASS == 0 ? BWD_IMGS0 : BWD_IMGS1) * IMG_BYTES;
     auto IMG = [&](int i) { return img + i * IMG_BYTES; };
     LdsWt<TM> W0(s_fr, lane);   // fenced per tile (the top of tile())

@@ -1,11 +1,11 @@
 // Field point query (nof_query_field): SDF, its gradient with respect to the point, and the colour
 // of the field at a list of points — the query side of NerfRunner: run_network_density(get_normals=
 // True) (nerf_runner.py:1306-1346) and run_network as mesh_vertex_color_from_network calls it
-// (:1411-1428, :1226-1303). Not a standalone header: field_step.hip includes it inside namespace nof
-// after k_query_sdf, whose shape it keeps — one wave per tile of 32 points, the levels split over the
+// (:1411-1428, :1226-1303). With it, above it, the SDF query it grew from (nof_query_sdf: k_query_sdf),
+// whose shape k_query_field keeps — one wave per tile of 32 points, the levels split over the
 // two lane halves by lane_level, all 46 weight fragments and the bias image staged in LDS, a
-// grid-stride loop over tiles — and whose device functions (gather_level, mlp_sdf_net,
-// mlp_colour_net, the fragment helpers) it uses as they are. No atomics; nothing is written but the
+// grid-stride loop over tiles. Both use field_core.h's device functions (gather_level, mlp_sdf_net,
+// mlp_colour_net, the fragment helpers) as they are. No atomics; nothing is written but the
 // requested output arrays.
 //
 // Per tile:
@@ -37,6 +37,91 @@
 //    features (the same corner reads, summed as the half kernel sums them) through both nets with the
 //    bias image rounded to fp16; the SDF keeps nof_query_sdf's bits.
 #pragma once
+#include "field_core.h"
+#pragma clang fp contract(off)
+
+namespace nof {
+
+// ------------------------------------------- SDF query (mesh extraction)
+// run_network_density (nerf_runner.py:1306-1346) on a dense grid or a point
+// list: clip to [-1,1], multires encode, sigma net (L1, ReLU, L2) -> sdf.
+// Grid mode follows extract_mesh (:1349-1382): point (i,j,k) = (gx[i], gy[j],
+// gz[k]) in meshgrid 'ij' order; points whose octree voxel at the ray-tracing
+// level is empty are not queried and read 1.0. One wave per 32 points; the
+// encode is spread over both lane halves exactly as in k_encode and the MLP
+// runs on MFMA with the weights staged in LDS.
+struct QueryArgs {
+    const float *pts;                  // [n,3] (point mode) or null
+    const float *gx, *gy, *gz;         // grid axes (grid mode)
+    int nx, ny, nz;
+    int64_t n;
+    const uint8_t *occ;                // [N^3] occupancy at the ray-tracing level (x fastest) or null
+    int occ_n;
+    float *sdf;                        // [n]
+};
+
+template <typename TM, typename TT>
+__global__ __launch_bounds__(256) void k_query_sdf(FieldArgs a, QueryArgs q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    TM *s_fr = reinterpret_cast<TM *>(smem);
+    float *s_b = staged_bias<TM, N_FRAGS>(smem);
+    NOF_STAGE_FRAGS(TM, N_FRAGS, 0, false, a, smem, s_b);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t ntile = (q.n + 31) / 32;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntile; t += (int64_t)gridDim.x * 4) {
+        const int64_t idx = t * 32 + n;
+        const bool inb = idx < q.n;
+        float x[3] = {0.f, 0.f, 0.f};
+        if (inb) {
+            if (q.pts) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) x[d] = q.pts[idx * 3 + d];
+            } else {
+                const int64_t k = idx % q.nz, ij = idx / q.nz;
+                const int64_t j = ij % q.ny, i = ij / q.ny;
+                x[0] = q.gx[i]; x[1] = q.gy[j]; x[2] = q.gz[k];
+            }
+        }
+        bool valid = inb;
+        if (inb && q.occ) {   // OctreeManager.get_center_ids >= 0 (Utils.py:392-394)
+            const float N = (float)q.occ_n;
+            uint32_t c[3];
+            bool inside = true;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                inside = inside && fabsf(x[d]) <= 1.f;
+                const float f = floorf((x[d] + 1.f) * 0.5f * N);
+                c[d] = (uint32_t)fminf(fmaxf(f, 0.f), N - 1.f);
+            }
+            valid = inside && q.occ[((size_t)c[2] * q.occ_n + c[1]) * q.occ_n + c[0]] != 0;
+        }
+        if (!__any(valid)) {
+            if (inb && h == 0) q.sdf[idx] = 1.f;
+            continue;
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) x[d] = fminf(fmaxf(x[d], -1.f), 1.f);   // torch.clip(inputs, -1, 1)
+        const float x01[3] = {(x[0] + 1) / 2, (x[1] + 1) / 2, (x[2] + 1) / 2};
+        Acts<TM> A;
+#pragma unroll
+        for (int ss = 0; ss < 2; ++ss) {
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) {
+                const int lv = lane_level(ss, qq, h);
+                float v[2] = {0.f, 0.f};
+                if (inb && lv < (int)a.L) encode_level<TT>(a, level_info(a, lv), x01, v);
+                frag_set<TM>(A.X[ss], 2 * qq, v[0]);
+                frag_set<TM>(A.X[ss], 2 * qq + 1, v[1]);
+            }
+        }
+        float sdf;
+        f16v l2;
+        mlp_sdf_net<TM>(LdsW<TM>{s_fr}, s_b, A, lane, sdf, l2);
+        if (inb && h == 0) q.sdf[idx] = valid ? sdf : 1.f;
+    }
+}
 
 struct QueryFieldArgs {
     const float *pts;      // [n,3]
@@ -47,8 +132,6 @@ struct QueryFieldArgs {
     float *grad;           // [n,3] or null
     float *rgb;            // [n,3] or null
 };
-
-__device__ __forceinline__ float round_h(float v) { return (float)(_Float16)v; }
 
 // encode_level (the same sums in the same order: the same feature bits) and, when `dx`, the level's
 // d feature / d x01 [axis][channel]; fh (amp, when `hm`): the feature as the reference's half kernel
@@ -243,22 +326,14 @@ __global__ __launch_bounds__(256) void k_query_field(FieldArgs a, QueryFieldArgs
     constexpr bool HALF = sizeof(TM) == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     TM *s_fr = reinterpret_cast<TM *>(smem);
-    float *s_b = reinterpret_cast<float *>(smem + N_FRAGS * 64 * 8 * sizeof(TM));
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.frags);
-        uint4 *dst = reinterpret_cast<uint4 *>(s_fr);
-        for (int i = threadIdx.x; i < N_FRAGS * 64 * 8 * (int)sizeof(TM) / 16; i += blockDim.x) dst[i] = src[i];
-        // amp: a second bias image rounded to fp16 (autocast's bias) for the colour pass
-        for (int i = threadIdx.x; i < 5 * 64; i += blockDim.x) {
-            s_b[i] = a.bias[i];
-            if constexpr (HALF) s_b[5 * 64 + i] = round_h(a.bias[i]);
-        }
-    }
+    float *s_b = staged_bias<TM, N_FRAGS>(smem);
+    // amp: a second bias image rounded to fp16 (autocast's bias) for the colour pass
+    NOF_STAGE_FRAGS(TM, N_FRAGS, 0, HALF, a, smem, s_b);
     __syncthreads();
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const LdsW<TM> W{s_fr};
-    const float *s_bc = HALF ? s_b + 5 * 64 : s_b;   // the colour pass's bias image
+    const float *s_bc = HALF ? s_b + BIAS_WORDS : s_b;   // the colour pass's bias image
     const bool want_dx = q.grad != nullptr, want_sdf = q.sdf != nullptr || want_dx, want_rgb = q.rgb != nullptr;
     const int64_t ntile = (q.n + 31) / 32;
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntile; t += (int64_t)gridDim.x * 4) {
@@ -285,3 +360,5 @@ __global__ __launch_bounds__(256) void k_query_field(FieldArgs a, QueryFieldArgs
         }
     }
 }
+
+}  // namespace nof

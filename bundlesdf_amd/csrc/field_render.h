@@ -1,9 +1,8 @@
 // Forward-only ray render (nof_render_rays): what NerfRunner.render_images needs of render_rays
 // (nerf_runner.py:1043-1087), raw2outputs (:1131-1168) and the depth rule of render_images (:602-610),
 // without anything of the training step: no tile records for a backward, no feature stores, no flags,
-// no losses, no atomics. Included in place by field_step.hip (same translation unit: it reuses the
-// step's device functions — sample_z, sample_point, encode_levels, mlp_sdf_net, mlp_colour_net,
-// bell_weight — as they are).
+// no losses, no atomics. It uses the device functions the step uses, from field_core.h — sample_z,
+// sample_point, encode_levels, mlp_sdf_net, mlp_colour_net, bell_weight — as they are.
 //
 //  * k_render_ctx: a thread per ray — the per-ray context record (store_ray_ctx) in the render's
 //    own workspace.
@@ -23,6 +22,10 @@
 // sample, colour net 2 x (32 x 64 + 64 x 64 + 64 x 16) = 14.3 K per sample of a colour tile (the K and
 // M paddings of the MFMA tiles included): 1.2 M (sigma, 192 samples) + 0.46 M per colour tile.
 #pragma once
+#include "field_core.h"
+#pragma clang fp contract(off)
+
+namespace nof {
 
 struct RenderOut {
     float *rgb;        // [R,3]
@@ -38,11 +41,10 @@ struct RenderOut {
 constexpr int RREC = 12;
 enum { RF_NONPOS = 1, RF_NEG = 2 };   // some in-tile product is not > 0 / is < 0
 
-// fragments FR_L1 .. FR_B5 - 1 (the forward's 24 of the 46) and the bias image, staged once per block
+// fragments FR_L1 .. FR_B5 - 1 (the forward's 24 of the 46) and the bias image, staged once per block;
+// behind them the waves' level tables (16 levels x 32 B each)
 constexpr int RENDER_NFR = FR_B5, RENDER_WPB = 8;
-template <typename TM> __host__ __device__ constexpr size_t render_lds_bytes() {
-    return (size_t)RENDER_NFR * 64 * 8 * sizeof(TM) + 5 * 64 * sizeof(float) + RENDER_WPB * 16 * 32;
-}
+constexpr size_t RENDER_LVT_BYTES = RENDER_WPB * 16 * 32;
 
 __global__ __launch_bounds__(256) void k_render_ctx(FieldArgs a) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,16 +55,11 @@ template <typename TM, typename TT>
 __global__ __launch_bounds__(RENDER_WPB * 64) void k_render(FieldArgs a, RenderOut o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const TM *s_fr = reinterpret_cast<const TM *>(smem);
-    float *s_b = reinterpret_cast<float *>(smem + RENDER_NFR * 64 * 8 * sizeof(TM));
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.frags);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem);
-        for (int i = threadIdx.x; i < RENDER_NFR * 64 * 8 * (int)sizeof(TM) / 16; i += blockDim.x) dst[i] = src[i];
-        for (int i = threadIdx.x; i < 5 * 64; i += blockDim.x) s_b[i] = a.bias[i];
-    }
+    float *s_b = staged_bias<TM, RENDER_NFR>(smem);
+    NOF_STAGE_FRAGS(TM, RENDER_NFR, 0, false, a, smem, s_b);
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint4 *lvt = reinterpret_cast<uint4 *>(smem + RENDER_NFR * 64 * 8 * sizeof(TM) + 5 * 64 * sizeof(float)) + wave * 32;
+    uint4 *lvt = reinterpret_cast<uint4 *>(smem + staged_bytes<TM, RENDER_NFR>()) + wave * 32;
     level_table(a, lvt, lane);
     __syncthreads();
     const int ntiles = a.S / 32;
@@ -166,3 +163,5 @@ __global__ __launch_bounds__(256) void k_render_final(FieldArgs a, RenderOut o) 
     for (int cc = 0; cc < 3; ++cc) o.rgb[(size_t)r * 3 + cc] = racc[cc] / (wtot + 1e-10f);
     o.depth[r] = all_pos ? a.far_sc : zj;
 }
+
+}  // namespace nof

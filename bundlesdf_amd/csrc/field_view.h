@@ -1,7 +1,7 @@
 // Free-camera surface render (nof_render_view): depth, normal and colour of the field's zero level
-// set from any pose — no pool ray, no frame depth. Included in place by field_step.hip (same
-// translation unit: it uses trace_ray_emit, encode_level, mlp_sdf_net and field_query.h's query_tile
-// as they are). Forward only: nothing is written but the outputs and the call's own workspace.
+// set from any pose — no pool ray, no frame depth. It uses ray_trace.h's trace_ray_emit, field_core.h's
+// encode_level and mlp_sdf_net and field_query.h's query_tile as they are. Forward only: nothing is
+// written but the outputs and the call's own workspace.
 //
 // Per pixel, all in fp32 with every written operation rounded on its own (contraction off, correctly
 // rounded division and square root), so that a float32 restatement on the host (tests/view_oracle.py)
@@ -39,11 +39,15 @@
 // colour net (14.3 K). Records: 32 B ray + 8 B per interval + 32 B bracket written and read once;
 // outputs 37 B.
 #pragma once
+#include "field_core.h"
+#include "field_query.h"
 
 // every operation of the positions rounds on its own: plain operators with contraction off (HIP's
 // __fmul_rn / __fadd_rn are inline wrappers compiled under the default mode: their product and sum may
 // still fuse into an FMA after inlining, so they are not used)
 #pragma clang fp contract(off)
+
+namespace nof {
 
 constexpr int VRAY = 8, VBRK = 8;
 enum { VF_MISS = 0, VF_BRACKET = 1, VF_INSIDE = 2 };
@@ -130,13 +134,8 @@ template <typename TM, typename TT>
 __global__ __launch_bounds__(256) void k_view_march(FieldArgs a, ViewArgs v) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     TM *s_fr = reinterpret_cast<TM *>(smem);
-    float *s_b = reinterpret_cast<float *>(smem + VIEW_NFR * 64 * 8 * sizeof(TM));
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.frags);
-        uint4 *dst = reinterpret_cast<uint4 *>(s_fr);
-        for (int i = threadIdx.x; i < VIEW_NFR * 64 * 8 * (int)sizeof(TM) / 16; i += blockDim.x) dst[i] = src[i];
-        for (int i = threadIdx.x; i < 5 * 64; i += blockDim.x) s_b[i] = a.bias[i];
-    }
+    float *s_b = staged_bias<TM, VIEW_NFR>(smem);
+    NOF_STAGE_FRAGS(TM, VIEW_NFR, 0, false, a, smem, s_b);
     __syncthreads();
     const int lane = threadIdx.x & 63, n = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -203,22 +202,14 @@ __global__ __launch_bounds__(256) void k_view_shade(FieldArgs a, ViewArgs v) {
     constexpr bool HALF = sizeof(TM) == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     TM *s_fr = reinterpret_cast<TM *>(smem);
-    float *s_b = reinterpret_cast<float *>(smem + N_FRAGS * 64 * 8 * sizeof(TM));
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.frags);
-        uint4 *dst = reinterpret_cast<uint4 *>(s_fr);
-        for (int i = threadIdx.x; i < N_FRAGS * 64 * 8 * (int)sizeof(TM) / 16; i += blockDim.x) dst[i] = src[i];
-        // amp: the colour pass's bias image rounded to fp16, as in k_query_field
-        for (int i = threadIdx.x; i < 5 * 64; i += blockDim.x) {
-            s_b[i] = a.bias[i];
-            if constexpr (HALF) s_b[5 * 64 + i] = round_h(a.bias[i]);
-        }
-    }
+    float *s_b = staged_bias<TM, N_FRAGS>(smem);
+    // amp: the colour pass's bias image rounded to fp16, as in k_query_field
+    NOF_STAGE_FRAGS(TM, N_FRAGS, 0, HALF, a, smem, s_b);
     __syncthreads();
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const LdsW<TM> W{s_fr};
-    const float *s_bc = HALF ? s_b + 5 * 64 : s_b;
+    const float *s_bc = HALF ? s_b + BIAS_WORDS : s_b;
     const int ntile = (v.n + 31) / 32;
     for (int tl = (int)blockIdx.x * 4 + wave; tl < ntile; tl += (int)gridDim.x * 4) {
         const int idx = tl * 32 + n;
@@ -277,3 +268,5 @@ __global__ __launch_bounds__(256) void k_view_shade(FieldArgs a, ViewArgs v) {
         }
     }
 }
+
+}  // namespace nof

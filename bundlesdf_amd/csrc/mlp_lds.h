@@ -2,7 +2,7 @@
 //
 // A 32x32x16 f16 MFMA operand fragment in the "normal" layout of the MLP chain holds, in lane
 // n + 32 h (n = sample of the tile), element j of K step s = unit 16 s + 8 (j >> 2) + 4 h +
-// (j & 3) of a 32-unit block (the accumulator row order, field_step.hip acc_row). The weight
+// (j & 3) of a 32-unit block (the accumulator row order, field_core.h acc_row). The weight
 // gradients need the same values with the samples as K: lane = unit, element j = sample
 // 16 ks + 8 h + j. Instead of recomputing every activation / gradient a second time with the
 // MFMA operands swapped (and converting it again), the normal fragment is written once into

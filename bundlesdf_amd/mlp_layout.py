@@ -2,7 +2,7 @@
 built at nerf_runner.py:221 with num_layers=2, hidden 64, geo 15, colour 3
 layers, input 32 = L*C, views 9 = SH degree 3).
 
-The fused field kernel (csrc/field_step.hip) keeps activations transposed —
+The field kernels (the MLP forward in csrc/field_core.h) keep activations transposed —
 features on MFMA rows (accumulator registers), the wave's 32 samples on MFMA
 columns (lanes) — and runs v_mfma_f32_32x32x16_f16 (amp) or
 v_mfma_f32_32x32x2_f32 (fp32) tiles. A layer whose input is the previous

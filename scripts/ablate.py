@@ -13,7 +13,7 @@ import bench  # noqa: E402
 from bundlesdf_amd.fused import FusedStep  # noqa: E402
 
 ONLY = os.environ.get("ONLY")
-# timing-build ablation bits (field_step.hip ABL(); results invalid when set)
+# timing-build ablation bits (field_core.h ABL(), used by field_step.hip; results invalid when set)
 MASKS = {"full": 0, "no_scatter_table": 1, "esig_no_rec": 2, "no_encode_gather": 8, "esig_sync_staging": 16,
          "no_backward_level": 32, "esig_no_barrier": 64, "flush_no_hbm": 128, "esig_no_sigma_mfma": 256,
          "esig_no_barrier_no_mfma": 64 | 256, "enc_no_quads": 512, "f32_scan": 4096, "no_counters": 16384,

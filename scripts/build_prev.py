@@ -3,7 +3,9 @@ current timing-build objects of the other sources -> bundlesdf_amd/libnof_prev.s
 scripts/gpu_ab.sh A/B runs against libnof_ablate.so (PROD=1: production builds, against libnof.so).
 REV must not predate the nof_field_desc that dropped the deleted kernels' selector fields: an
 older field_step.hip names those fields and does not compile against the current include/nof.h
-(and a library built from the older header is refused at load: nof_field_desc_size).
+(and a library built from the older header is refused at load: nof_field_desc_size). Nor may it
+predate the split of the inference side into field_infer.hip: an older field_step.hip defines the
+query and render entry points too, which the current field_infer object already holds.
 Usage: [PROD=1] python scripts/build_prev.py [REV]"""
 import glob
 import os
@@ -17,12 +19,15 @@ os.environ["NOF_ABLATE"] = "0" if os.environ.get("PROD") == "1" else "1"
 from bundlesdf_amd import build as B  # noqa: E402
 
 rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
+if subprocess.run(["git", "-C", ROOT, "cat-file", "-e", f"{rev}:bundlesdf_amd/csrc/field_infer.hip"]).returncode != 0:
+    sys.exit(f"{rev} predates csrc/field_infer.hip (see the docstring)")
 B.build()
 # FILES: the csrc sources taken from REV (default field_step.hip); HEADERS: csrc headers taken from REV
-# as well (default field_mlp_bwd.h, the MLP backward kernels field_step.hip includes in place; skipped
-# when REV predates them) — placed first on the include path; the rest from the working tree
+# as well (default field_mlp_bwd.h, the MLP backward kernels field_step.hip includes in place, and
+# field_core.h / field_host.h, the device core and host helpers it shares with field_infer.hip; each
+# skipped when REV predates it) — placed first on the include path; the rest from the working tree
 files = os.environ.get("FILES", "field_step.hip").split(",")
-headers = os.environ.get("HEADERS", "field_mlp_bwd.h").split(",")
+headers = os.environ.get("HEADERS", "field_mlp_bwd.h,field_core.h,field_host.h").split(",")
 inc = "/tmp/nof_prev_inc"
 os.makedirs(inc, exist_ok=True)
 for fn in os.listdir(inc):

@@ -1,5 +1,6 @@
 # Register / LDS / spill summary of every kernel in one csrc file (device-only compile, readelf notes).
-# Usage: bash scripts/kernel_resources.sh field_step [regex]
+# Usage: bash scripts/kernel_resources.sh field_step [regex]   (the training step's kernels; field_infer: the
+# query and render kernels)
 set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${TMPDIR:-/tmp}/nof_res_$1.co
