@@ -75,6 +75,8 @@ _SIGNATURES = {
     "nof_texture_accumulate": ([_p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p], _int),
     "nof_vertex_color_accumulate": ([_p, _i32, _i32, _p, _f32, _p, _p, _p, _p, _p, _i64, ctypes.c_double, _p, _p, _p, _p,
                                      _p], _int),
+    "nof_render_mesh_workspace_bytes": ([_i32, _i64, _i32, _i32], ctypes.c_size_t),
+    "nof_render_mesh": ([_p, _p], _int),
     "nof_segment_mean": ([_p, _i32, _p, _p, _i32, _p, _p], _int),
     "nof_dbscan": ([_p, _i32, ctypes.c_double, _i32, _p, _p, _p, _p, _p], _int),
     "nof_marching_cubes_blocks": ([_i32, _i32, _i32, _p], _int),
@@ -133,6 +135,19 @@ class ViewOut(ctypes.Structure):
     """Mirror of nof_view_out (include/nof.h): the outputs of nof_render_view."""
     _fields_ = [("t", _p), ("depth", _p), ("normal", _p), ("rgb", _p), ("hit", _p), ("index", _p), ("tiles", _p),
                 ("workspace", _p)]
+
+
+MESH_COLOUR_FLAT, MESH_COLOUR_VERTEX, MESH_COLOUR_TEXTURE = 0, 1, 2   # NOF_MESH_COLOUR_*
+
+
+class MeshRenderDesc(ctypes.Structure):
+    """Mirror of nof_mesh_render_desc (include/nof.h): the mesh, poses, camera and outputs of nof_render_mesh."""
+    _d = ctypes.c_double
+    _fields_ = [("vertices", _p), ("faces", _p), ("n_vertices", _i64), ("n_faces", _i64), ("colors", _p),
+                ("normals", _p), ("uv", _p), ("texture", _p), ("tex_h", _i32), ("tex_w", _i32), ("ob_in_cam", _p),
+                ("K", _p), ("B", _i32), ("H", _i32), ("W", _i32), ("znear", _d), ("zfar", _d), ("colour_mode", _i32),
+                ("shade", _i32), ("base_rgb", ctypes.c_uint8 * 4), ("small_max_pixels", _i32), ("workspace", _p),
+                ("depth", _p), ("face", _p), ("rgb", _p), ("normal", _p)]
 
 
 class StepParams(ctypes.Structure):

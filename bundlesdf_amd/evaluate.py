@@ -24,7 +24,7 @@ from .mesh import trimesh_clean, trimesh_split
 
 __all__ = ["PointGrid", "nearest", "add_err", "adi_err", "compute_auc", "chamfer_distance_between_clouds_mutual",
            "sample_surface", "icp_point_to_point", "correspondence_moments", "align_first_frame", "evaluate_poses",
-           "evaluate_mesh"]
+           "evaluate_mesh", "mesh_frame_agreement"]
 
 MAX_GRID_CELLS = 1 << 24
 RIGID_TOL = 1e-6          # max |R R^T - I| of a pose add_err / adi_err accept
@@ -369,3 +369,37 @@ def evaluate_mesh(pred_mesh, gt_pts, voxel=0.005, n_samples=99999, icp_thres=0.0
     moved = (pts @ T[:3, :3].T + T[:3, 3]).contiguous()
     cd = chamfer_distance_between_clouds_mutual(moved, gt_grid) * 100
     return {"chamfer_cm": cd, "icp": icp, "component": best}
+
+
+def mesh_frame_agreement(render_depth, render_mask, obs_depth, obs_mask, max_depth):
+    """How well a rendered mesh (MeshRenderer.render's depth and mask) coincides with observed frames,
+    per frame: [H,W] or [F,H,W] arrays or tensors on any device -> {"iou", "depth_mean", "depth_median"
+    (float64 [F]) and "count" (int64 [F])}, tensors on the inputs' device.
+
+    A rendered pixel is valid where its mask is set and 0 < depth <= max_depth; an observed one
+    likewise (the frames' 0 and their far fill both fall out). iou is the intersection of the two
+    valid sets over their union; depth_mean / depth_median are the mean and the median (the lower of
+    the two middle values for an even count) of |rendered - observed| over the intersection, count
+    is its size. A frame with an empty intersection reports iou 0 (also when the union is empty),
+    count 0 and differences 0: no NaN."""
+    def t(a):
+        return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    rd, rm, od, om = t(render_depth), t(render_mask), t(obs_depth), t(obs_mask)
+    dev = rd.device
+    H, W = rd.shape[-2:]
+    rd, od = rd.reshape(-1, H * W).double(), od.to(dev).reshape(-1, H * W).double()
+    rm, om = rm.to(dev).reshape(-1, H * W) != 0, om.to(dev).reshape(-1, H * W) != 0
+    if not (rd.shape == od.shape == rm.shape == om.shape):
+        raise ValueError("mesh_frame_agreement: the four images must have one shape")
+    a = rm & (rd > 0) & (rd <= max_depth)
+    b = om & (od > 0) & (od <= max_depth)
+    both = a & b
+    count = both.sum(1)
+    union = (a | b).sum(1)
+    iou = torch.where(union > 0, count.double() / union.clamp(min=1).double(), torch.zeros_like(count, dtype=torch.float64))
+    diff = torch.where(both, (rd - od).abs(), torch.full_like(rd, float("inf")))
+    mean = torch.where(both, diff, torch.zeros_like(diff)).sum(1) / count.clamp(min=1).double()
+    srt = torch.sort(diff, dim=1).values                       # the intersection's differences first
+    mid = ((count - 1).clamp(min=0) // 2)[:, None]
+    median = torch.where(count > 0, srt.gather(1, mid)[:, 0], torch.zeros_like(mean))
+    return {"iou": iou, "depth_mean": mean, "depth_median": median, "count": count}

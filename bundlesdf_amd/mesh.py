@@ -267,6 +267,147 @@ class Mesh:
             raise ValueError("Mesh.export: .obj or .ply")
 
 
+    @staticmethod
+    def load(path):
+        """Read a .obj that Mesh.export wrote: `v x y z [r g b]` (colours in [0, 1] -> uint8), `vn`, `vt`,
+        faces `f a b c` with corners `a`, `a/a`, `a//a` or `a/a/a` (one index for position, uv and normal: the
+        attributes are per vertex), and `mtllib` -> the .mtl beside the file -> `map_Kd` -> the .png
+        beside it as the texture. `usemtl`, blank lines and `#` comments are skipped; anything else raises
+        ValueError naming the file and line."""
+        import os
+
+        def bad(no, line, why):
+            return ValueError(f"Mesh.load: {path}:{no}: {why}: {line.strip()!r}")
+
+        def floats(no, line, tok, counts):
+            try:
+                vals = [float(x) for x in tok]
+            except ValueError:
+                raise bad(no, line, "not a number") from None
+            if len(vals) not in counts or not np.isfinite(vals).all():
+                raise bad(no, line, f"expected {' or '.join(str(c) for c in counts)} finite numbers")
+            return vals
+
+        if not path.endswith(".obj"):
+            raise ValueError("Mesh.load: .obj")
+        v, vc, vn, vt, faces, mtl = [], [], [], [], [], None
+        with open(path) as fh:
+            for no, line in enumerate(fh, 1):
+                tok = line.split()
+                if not tok or tok[0].startswith("#") or tok[0] == "usemtl":
+                    continue
+                if tok[0] == "v":
+                    vals = floats(no, line, tok[1:], (3, 6))
+                    v.append(vals[:3])
+                    if len(vals) == 6:
+                        vc.append(vals[3:])
+                    if len(vc) not in (0, len(v)):
+                        raise bad(no, line, "some vertices carry a colour and some do not")
+                elif tok[0] == "vn":
+                    vn.append(floats(no, line, tok[1:], (3,)))
+                elif tok[0] == "vt":
+                    vt.append(floats(no, line, tok[1:], (2,)))
+                elif tok[0] == "f":
+                    if len(tok) != 4:
+                        raise bad(no, line, "a face must have three corners")
+                    corner = []
+                    for t in tok[1:]:
+                        parts = t.split("/")
+                        idx = [p for p in parts if p != ""]
+                        if len(parts) > 3 or not idx or not all(p.isdigit() for p in idx) or len(set(idx)) != 1 \
+                                or parts[0] == "" or int(idx[0]) < 1:
+                            raise bad(no, line, "a corner must be a, a/a, a//a or a/a/a with a >= 1")
+                        corner.append(int(idx[0]) - 1)
+                    faces.append(corner)
+                elif tok[0] == "mtllib" and len(tok) == 2:
+                    mtl = tok[1]
+                else:
+                    raise bad(no, line, "unsupported line")
+        n = len(v)
+        f = np.asarray(faces, np.int64).reshape(-1, 3)
+        if len(f) and int(f.max()) >= n:
+            raise ValueError(f"Mesh.load: {path}: a face names vertex {int(f.max()) + 1} of {n}")
+        for name, rows in (("vn", vn), ("vt", vt)):
+            if rows and len(rows) != n:
+                raise ValueError(f"Mesh.load: {path}: {len(rows)} {name} lines for {n} vertices")
+        mesh = Mesh(np.asarray(v, np.float64).reshape(-1, 3), f)
+        if vc:
+            mesh.vertex_colors = np.clip(np.rint(np.asarray(vc) * 255.0), 0, 255).astype(np.uint8)
+        if vn:
+            mesh.vertex_normals = np.asarray(vn, np.float64)
+        if vt:
+            mesh.uv = np.asarray(vt, np.float64)
+        if mtl is not None:
+            folder = os.path.dirname(path)
+            image = None
+            with open(os.path.join(folder, mtl)) as fh:
+                for no, line in enumerate(fh, 1):
+                    tok = line.split()
+                    if tok and tok[0] == "map_Kd":
+                        if len(tok) != 2:
+                            raise ValueError(f"Mesh.load: {os.path.join(folder, mtl)}:{no}: map_Kd takes one file name: "
+                                             f"{line.strip()!r}")
+                        image = tok[1]
+            if image is not None:
+                mesh.texture = read_png(os.path.join(folder, image))
+        return mesh
+
+
+def read_png(path):
+    """The uint8 [H,W,3] image of an 8-bit RGB, non-interlaced PNG (what write_png writes; every
+    row filter is undone). Anything else raises ValueError."""
+    import struct
+    import zlib
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"read_png: {path} is not a PNG file")
+    pos, head, idat = 8, None, b""
+    while pos + 8 <= len(data):
+        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat += body
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if head is None or head[2:] != (8, 2, 0, 0, 0):
+        raise ValueError(f"read_png: {path}: only 8-bit RGB without interlacing is read")
+    W, H = head[:2]
+    raw = np.frombuffer(zlib.decompress(idat), np.uint8)
+    if raw.size != H * (1 + 3 * W):
+        raise ValueError(f"read_png: {path}: {raw.size} bytes of image data for {W}x{H}")
+    raw = raw.reshape(H, 1 + 3 * W)
+    if not raw[:, 0].any():                       # filter 0 on every row
+        return raw[:, 1:].reshape(H, W, 3).copy()
+    out = np.zeros((H, 3 * W), np.int64)
+    for r in range(H):
+        ft, row = int(raw[r, 0]), raw[r, 1:].astype(np.int64)
+        up = out[r - 1] if r else np.zeros(3 * W, np.int64)
+        if ft == 0:
+            out[r] = row
+        elif ft == 2:
+            out[r] = (row + up) & 255
+        elif ft in (1, 3, 4):
+            for x in range(3 * W):
+                a = out[r, x - 3] if x >= 3 else 0
+                b, c = up[x], (up[x - 3] if x >= 3 else 0)
+                if ft == 1:
+                    pred = a
+                elif ft == 3:
+                    pred = (a + b) // 2
+                else:
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if pa <= pb and pa <= pc else b if pb <= pc else c
+                out[r, x] = (row[x] + pred) & 255
+        else:
+            raise ValueError(f"read_png: {path}: row {r} has filter type {ft}")
+    return out.astype(np.uint8).reshape(H, W, 3)
+
+
 def write_png(path, img):
     """8-bit RGB PNG (zlib, no external imaging library)."""
     import struct

@@ -596,6 +596,27 @@ class NerfRunner:
             out["t"], out["depth"] = out["t"] / sc, out["depth"] / sc
         return out
 
+    def render_mesh(self, mesh, frame_ids=None, metres=False, **kw):
+        """A normalised-space mesh (extract_mesh's) drawn at the runner's frames (bundlesdf_amd.mesh_render):
+        the optimised poses (texture._cvcam_in_obs: c2w_array with the learned corrections) inverted,
+        the runner's K, H, W, znear 0.1 and zfar = far * sc_factor as the texture pass uses them.
+        frame_ids: None (every frame), an index or a list. Returns numpy images {"depth" float32,
+        "face" int32, "mask" bool [N,H,W], "rgb" uint8, "normal" float32 [N,H,W,3]} ([H,W] / [H,W,3] for
+        a single index); metres=True divides depth by sc_factor. kw: MeshRenderer.render's colour,
+        shade, small_max_pixels. The reference's counterpart is ModelRendererOffscreen at the
+        tracked poses (offscreen_renderer.py)."""
+        from .mesh_render import MeshRenderer
+        from .texture import _cvcam_in_obs
+        single = frame_ids is not None and np.ndim(frame_ids) == 0
+        ids = np.arange(len(self.images)) if frame_ids is None else np.atleast_1d(np.asarray(frame_ids, np.int64))
+        ob_in_cams = np.linalg.inv(_cvcam_in_obs(self)[ids])
+        sc = self.cfg["sc_factor"]
+        r = MeshRenderer(mesh, self.K, self.H, self.W, znear=0.1, zfar=self.cfg["far"] * sc, device=self.device)
+        out = {k: v.cpu().numpy() for k, v in r.render(ob_in_cams, **kw).items()}
+        if metres:
+            out["depth"] = out["depth"] / np.float32(sc)
+        return {k: v[0] for k, v in out.items()} if single else out
+
     def get_truncation(self):
         """nerf_runner.py:661-674: the truncation band of the current step (linear / exp
         annealing from trunc_start when trunc_decay_type is set), times sc_factor."""

@@ -630,6 +630,48 @@ int nof_vertex_color_accumulate(const uint64_t *zbuf, int32_t H, int32_t W, cons
                                 double *nearest_dist,     /* [Nv] f64 or NULL: its distance, +inf = none */
                                 void *stream);
 
+/* Mesh render: depth, face id, colour and normal images of a triangle mesh at B poses in one call
+ * (the reference's pyrender pass, offscreen_renderer.py: ModelRendererOffscreen). The z-buffer of
+ * every pose is nof_raster_faces' (the same projection, cull, coverage and depth arithmetic and
+ * the same 64-bit keys: ties in depth go to the lower face index), filled by two kernels: a lane
+ * per (pose, face) rasterises the faces whose clamped bounding box holds at most small_max_pixels
+ * pixels and lists the others, which a wave per listed face then rasterises 64 pixels at a
+ * time. A third kernel shades every pixel; mesh_render.hip states its order of operations. */
+enum { NOF_MESH_COLOUR_FLAT = 0, NOF_MESH_COLOUR_VERTEX = 1, NOF_MESH_COLOUR_TEXTURE = 2 };
+
+typedef struct {
+    const float *vertices;     /* device [n_vertices,3] f32, object frame */
+    const int64_t *faces;      /* device [n_faces,3] i64, every corner in [0, n_vertices) (the caller's duty) */
+    int64_t n_vertices;
+    int64_t n_faces;           /* >= 0, and B n_faces < 2^31 */
+    const uint8_t *colors;     /* device [n_vertices,3] u8 or NULL (needed by NOF_MESH_COLOUR_VERTEX) */
+    const float *normals;      /* device [n_vertices,3] f32 or NULL: NULL shades with the face normal */
+    const float *uv;           /* device [n_vertices,2] f32 or NULL (needed by NOF_MESH_COLOUR_TEXTURE) */
+    const uint8_t *texture;    /* device [tex_h,tex_w,3] u8 or NULL, row 0 = top (as bake_texture stores it) */
+    int32_t tex_h, tex_w;
+    const double *ob_in_cam;   /* device [B,4,4] f64 row-major: object in the OpenCV camera */
+    const double *K;           /* host [3,3] f64 row-major, read during the call */
+    int32_t B, H, W;           /* B H W < 2^31 */
+    double znear, zfar;        /* 0 < znear < zfar */
+    int32_t colour_mode;       /* NOF_MESH_COLOUR_* */
+    int32_t shade;             /* non-zero: the colour times |n . d|, d the unit pixel ray (a headlight) */
+    uint8_t base_rgb[4];       /* NOF_MESH_COLOUR_FLAT's colour (3 used) */
+    int32_t small_max_pixels;  /* >= 0: the largest bounding box the per-face lane rasterises itself */
+    void *workspace;           /* device, nof_render_mesh_workspace_bytes(B, n_faces, H, W) bytes */
+    float *depth;              /* device [B,H,W] f32: the z-buffer's depth, 0 on a miss */
+    int32_t *face;             /* device [B,H,W] i32: the face seen, -1 on a miss */
+    uint8_t *rgb;              /* device [B,H,W,3] u8, 0 on a miss */
+    float *normal;             /* device [B,H,W,3] f32: unit, camera frame, towards the camera; 0 on a miss */
+} nof_mesh_render_desc;
+
+size_t nof_render_mesh_workspace_bytes(int32_t B, int64_t n_faces, int32_t H, int32_t W);
+
+/* Two memsets and three launches on `stream`; nothing is read back. Every output pixel is written.
+ * The result depends on the inputs alone (the z-buffer is built with atomicMin, which is
+ * order-free): two calls give the same bits, and so does every small_max_pixels. The descriptor is
+ * validated before the first HIP call: NOF_EINVAL with nof_last_error naming the field. */
+int nof_render_mesh(const nof_mesh_render_desc *desc, void *stream);
+
 /* ------------------------------------------------------------------ group 6
  * Mesh extraction on the device: the marching cubes of
  * NerfRunner.extract_mesh (nerf_runner.py:1349-1408, skimage there) and the
