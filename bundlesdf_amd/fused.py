@@ -29,6 +29,7 @@ from . import mlp_layout as ML
 _F32, _F16 = 0, 1
 MAX_LEVEL_RES = 1023      # k_scatter's run keys: 10 bits per cell coordinate (field_step.hip)
 QUADS_MIN_RAYS = 32768    # nof_field_step's default quads_min_rays (the xy-quad mirror encode from this batch)
+MAX_POSE_FRAMES = 1024    # nof_pose_backward: k_pose_reduce's LDS image is F x 12 floats (pose.hip)
 
 
 def lr_at(cfg, global_step, base):
@@ -140,6 +141,10 @@ class FusedStep:
     def __init__(self, cfg, pool, c2w, occ, grid, mlp, pose_array, amp=None, frame_start=None, blocks_per_cu=0,
                  process_group=None, world_size=1, time_kernels=False, feature_array=None, exchange=None):
         # blocks_per_cu: accepted for callers that still pass it and ignored (the kernel whose grid it sized is gone)
+        # the frame limit first: otherwise it shows as 'pose_backward: bad arguments' after the first field
+        # pass (frozen poses, cfg optimize_poses = 0, never run the pose backward and take any F)
+        if c2w.shape[0] > MAX_POSE_FRAMES and bool(cfg.get("optimize_poses", 1)):
+            raise ValueError(f"fused path: {c2w.shape[0]} frames > {MAX_POSE_FRAMES} (nof_pose_backward's limit)")
         dev = pool.device
         if dev.type != "cuda":
             raise RuntimeError("FusedStep needs a HIP device (no CPU fallback)")
