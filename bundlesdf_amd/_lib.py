@@ -92,6 +92,8 @@ _SIGNATURES = {
                             _p], _int),
     "nof_nearest_workspace_bytes": ([_i32], ctypes.c_size_t),
     "nof_correspondence_moments": ([_p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p], _int),
+    "nof_ransac_workspace_bytes": ([_i32, _i64, _i32], ctypes.c_size_t),
+    "nof_ransac_pairs": ([_p, _p], _int),
 }
 
 
@@ -148,6 +150,17 @@ class MeshRenderDesc(ctypes.Structure):
                 ("K", _p), ("B", _i32), ("H", _i32), ("W", _i32), ("znear", _d), ("zfar", _d), ("colour_mode", _i32),
                 ("shade", _i32), ("base_rgb", ctypes.c_uint8 * 4), ("small_max_pixels", _i32), ("workspace", _p),
                 ("depth", _p), ("face", _p), ("rgb", _p), ("normal", _p)]
+
+
+class RansacDesc(ctypes.Structure):
+    """Mirror of nof_ransac_desc (include/nof.h): the correspondences, settings and outputs of nof_ransac_pairs."""
+    _d = ctypes.c_double
+    _fields_ = [("pts_a", _p), ("pts_b", _p), ("normals_a", _p), ("normals_b", _p), ("conf", _p), ("pair_start", _p),
+                ("max_trans_sq", _p), ("min_trace", _p), ("M", _i64), ("P", _i32), ("n_trials", _i32), ("seed", _u32),
+                ("min_inliers", _i32), ("inlier_dist_sq", _d), ("cos_normal", _d), ("workspace", _p),
+                ("workspace_bytes", ctypes.c_size_t), ("best_trial", _p), ("score", _p), ("pose", _p),
+                ("n_inliers", _p), ("inlier", _p), ("sums", _p), ("trial_idx", _p), ("trial_pose", _p),
+                ("trial_live", _p), ("trial_score", _p)]
 
 
 class StepParams(ctypes.Structure):

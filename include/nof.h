@@ -787,6 +787,91 @@ size_t nof_nearest_workspace_bytes(int32_t n);
 int nof_correspondence_moments(const double *source, int32_t n, const double *xform, const double *target, int32_t m,
                                const int32_t *index, const double *dist, double *sums, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------ group 8
+ * Match filtering: multi-pair RANSAC over 3-D correspondences (the reference's
+ * BundleTrack/src/cuda/cuda_ransac.cu behind SiftManager::runRansacMultiPairGPU:
+ * which matches between two frames agree with one rigid motion).
+ *
+ * The correspondences of P frame pairs are concatenated: pair p owns the rows
+ * pair_start[p] .. pair_start[p+1]-1 of pts_a / pts_b (n_p of them; the kernels
+ * clamp both ends into [0, M] and never read outside it). The model maps A onto
+ * B: b ~ R a + t. All arithmetic is f64 without contraction, in the order given
+ * here, so the scores and flags of a pose can be reproduced bit for bit.
+ *
+ * Sampling. h(x) on uint32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *   x *= 0x846ca68b; x ^= x >> 16. Draw j in {0,1,2} of trial t of pair p is
+ *   u = h((uint32)((p T + t) 3 + j) ^ h(seed)), the counter in wrapping uint32,
+ *   and the row is (uint64(u) n_p) >> 32, local to the pair. A trial with two
+ *   equal rows is dead (not redrawn); n_p < 3 makes every trial of the pair dead.
+ * Hypothesis. The least-squares rigid fit of the three sampled pairs (Horn's unit
+ *   quaternion: the eigenvector of the largest eigenvalue of the 4x4 matrix built
+ *   from sum (a - mean a)(b - mean b)^T, by cyclic Jacobi rotations; R from the
+ *   normalised quaternion, so it is a proper rotation for every sample, also a
+ *   collinear or repeated one; t = mean b - R mean a). It is held to a float64
+ *   SVD by tolerance, not bit for bit. A pose with a non-finite value is dead.
+ * Gates. A trial is dead unless (tx tx + ty ty) + tz tz <= max_trans_sq[p] and
+ *   (R00 + R11) + R22 >= min_trace[p] (= 1 + 2 cos(max_rot)); +inf / -inf switch
+ *   a gate off. Dead trials score 0.
+ * Inlier test of pose (R, t) and row i: q_k = ((R[k][0] ax + R[k][1] ay) +
+ *   R[k][2] az) + t[k]; d2 = (dx dx + dy dy) + dz dz with dx = bx - qx; inlier iff
+ *   d2 <= inlier_dist_sq and, with normals, (n'x mbx + n'y mby) + n'z mbz >=
+ *   cos_normal where n'_k = (R[k][0] nx + R[k][1] ny) + R[k][2] nz (the normal of
+ *   A rotated, not translated) and mb the normal of B.
+ * Score. w_i = (int64) rint(conf_i 65536) with 0 <= conf_i <= 32767 (the caller's
+ *   duty), 65536 without conf; a trial's score is the int64 sum of w_i over its
+ *   inliers, accumulated with integer atomics: the same bits on every run.
+ * Winner. Per pair the live trial of the highest score, the lowest trial among
+ *   equals. No live trial with a score above 0: best_trial -1, score 0, the
+ *   identity pose, no inliers.
+ * Flags. inlier[i] is the inlier test of the pair's winning pose; n_inliers[p]
+ *   their count. A pair with fewer than min_inliers inliers is cleared: flags 0,
+ *   n_inliers 0 and sums 0, while best_trial, score and pose stay.
+ * Sums. sums[p] has the layout of nof_correspondence_moments over the pair's
+ *   inliers with the identity transform: count, sum a (3), sum b (3), sum a b^T
+ *   (9, a's component first), sum d2 with d2 = (dx dx + dy dy) + dz dz, dx = bx -
+ *   ax. One block per pair: thread r of 256 adds its rows r, r + 256, ... in
+ *   order, a butterfly adds the lanes of a wave, the four waves are added in
+ *   order. No floating-point atomics: the same bits on every run.
+ */
+typedef struct {
+    const double *pts_a, *pts_b;          /* device [M,3] f64 */
+    const double *normals_a, *normals_b;  /* device [M,3] f64, both or neither */
+    const double *conf;                   /* device [M] f64 or NULL */
+    const int32_t *pair_start;            /* device [P+1] i32 */
+    const double *max_trans_sq;           /* device [P] f64 */
+    const double *min_trace;              /* device [P] f64 */
+    int64_t M;                            /* 0 <= M < 2^31 */
+    int32_t P;                            /* 1 .. 65535 */
+    int32_t n_trials;                     /* T: 1 .. 65536 */
+    uint32_t seed;
+    int32_t min_inliers;
+    double inlier_dist_sq;                /* >= 0 */
+    double cos_normal;                    /* used with normals only */
+    void *workspace;                      /* device, at least nof_ransac_workspace_bytes(P, M, n_trials) */
+    size_t workspace_bytes;               /* the size of workspace */
+    int32_t *best_trial;                  /* device [P] i32 */
+    int64_t *score;                       /* device [P] i64 */
+    double *pose;                         /* device [P,16] f64, 4x4 row-major */
+    int32_t *n_inliers;                   /* device [P] i32 */
+    uint8_t *inlier;                      /* device [M] u8 */
+    double *sums;                         /* device [P,17] f64 */
+    /* debug outputs, NULL = not written */
+    int32_t *trial_idx;                   /* device [P,T,3] i32: the rows drawn, local to the pair */
+    double *trial_pose;                   /* device [P,T,12] f64: rows of [R | t]; zeros for a trial dead by its draws */
+    uint8_t *trial_live;                  /* device [P,T] u8 */
+    int64_t *trial_score;                 /* device [P,T] i64 */
+} nof_ransac_desc;
+
+/* Per-trial poses, live flags and scores: no [T x n] array exists anywhere. */
+size_t nof_ransac_workspace_bytes(int32_t P, int64_t M, int32_t n_trials);
+
+/* Four launches on `stream`; nothing is allocated or read back. The whole descriptor is validated
+ * before the first HIP call: NOF_EINVAL with nof_last_error naming the field (P, n_trials and M
+ * ranges, normals given on one side only, a NULL output, a negative or NaN inlier_dist_sq, a NULL
+ * input or a workspace that is too small). M == 0 returns 0 at once without a launch: every pair is
+ * empty and the outputs are left as the caller filled them (best_trial -1, the identity, zeros). */
+int nof_ransac_pairs(const nof_ransac_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
