@@ -94,6 +94,8 @@ _SIGNATURES = {
     "nof_correspondence_moments": ([_p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p], _int),
     "nof_ransac_workspace_bytes": ([_i32, _i64, _i32], ctypes.c_size_t),
     "nof_ransac_pairs": ([_p, _p], _int),
+    "nof_pose_graph_workspace_bytes": ([_i32, _i32, _i64, _i32, _i32], ctypes.c_size_t),
+    "nof_pose_graph_optimize": ([_p, _p], _int),
 }
 
 
@@ -161,6 +163,20 @@ class RansacDesc(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_size_t), ("best_trial", _p), ("score", _p), ("pose", _p),
                 ("n_inliers", _p), ("inlier", _p), ("sums", _p), ("trial_idx", _p), ("trial_pose", _p),
                 ("trial_live", _p), ("trial_score", _p)]
+
+
+class PoseGraphDesc(ctypes.Structure):
+    """Mirror of nof_pose_graph_desc (include/nof.h): the poses, both terms, settings and outputs of
+    nof_pose_graph_optimize."""
+    _d = ctypes.c_double
+    _fields_ = [("poses", _p), ("fixed", _p), ("N", _i32), ("n_outer", _i32), ("n_inner", _i32), ("P", _i32),
+                ("M", _i64), ("pair_frames", _p), ("pts_a", _p), ("pts_b", _p), ("pair_start", _p), ("weight", _p),
+                ("points", _p), ("normals", _p), ("H", _i32), ("W", _i32), ("radius", _i32), ("reserved", _i32),
+                ("fx", _d), ("fy", _d), ("cx", _d), ("cy", _d), ("robust_delta", _d), ("w_sparse", _d),
+                ("w_dense", _d), ("dist_thresh", _d), ("normal_thresh", _d), ("depth_min", _d), ("depth_max", _d),
+                ("min_trace", _d), ("workspace", _p), ("workspace_bytes", ctypes.c_size_t), ("poses_out", _p),
+                ("history", _p), ("iter_poses", _p), ("dbg_A", _p), ("dbg_g", _p), ("dbg_delta", _p),
+                ("dense_index", _p)]
 
 
 class StepParams(ctypes.Structure):

@@ -872,6 +872,76 @@ size_t nof_ransac_workspace_bytes(int32_t P, int64_t M, int32_t n_trials);
  * empty and the outputs are left as the caller filled them (best_trial -1, the identity, zeros). */
 int nof_ransac_pairs(const nof_ransac_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 9
+ * Pose-graph optimisation over a window of N <= 128 frames (the reference's
+ * CUDASolverBundling behind Bundler::optimizeGPU): n_outer Gauss-Newton steps over
+ * camera-in-world poses, each one linearisation of a Huber-robust point-to-point
+ * term over sparse matches (the layout of group 8: pair p owns rows pair_start[p] ..
+ * pair_start[p+1]-1 of pts_a / pts_b, points of frame pair_frames[p] = (i, j) in
+ * their cameras) plus a Huber-robust projective point-to-plane term between the
+ * point / normal maps of every active pair of frames, n_inner steps of
+ * Jacobi-preconditioned conjugate gradients on the explicit system, and the update
+ * T_k <- Exp(delta_k) T_k. The definition, with the order of every operation, is
+ * the header comment of bundlesdf_amd/csrc/pose_graph.hip. All arithmetic is f64
+ * without contraction, every sum has a fixed order and no floating-point atomics
+ * are used: the same bytes on every run. Iteration counts are fixed: no early
+ * exit, nothing read back by the host.
+ *
+ * Either term may be absent (P == 0: no sparse term; points == NULL: no dense
+ * term), not both. A frame with fixed[k] != 0 is a constant: its pose comes back
+ * bit for bit, its rows and columns of A and g are zero. The caller makes sure at
+ * least one frame is fixed (the gauge), that pair_start is monotone inside [0, M]
+ * and that pair_frames names two different frames of 0 .. N-1; the kernels clamp
+ * and skip rather than read outside an array.
+ *
+ * history [n_outer+1, 4] f64: sparse energy, dense energy, live sparse rows (weight
+ * != 0), dense correspondences, at each linearisation and at the final poses. */
+typedef struct {
+    const double *poses;                  /* device [N,16] f64, 4x4 row-major camera-in-world */
+    const uint8_t *fixed;                 /* device [N] u8 */
+    int32_t N;                            /* 1 .. 128 */
+    int32_t n_outer;                      /* 1 .. 1024 */
+    int32_t n_inner;                      /* 0 .. 1024 */
+    int32_t P;                            /* sparse pairs, 0 .. 65535 */
+    int64_t M;                            /* sparse rows, 0 <= M < 2^31 */
+    const int32_t *pair_frames;           /* device [P,2] i32 */
+    const double *pts_a, *pts_b;          /* device [M,3] f64 */
+    const int32_t *pair_start;            /* device [P+1] i32 */
+    const double *weight;                 /* device [M] f64 or NULL (= 1); 0 drops the row */
+    const float *points, *normals;        /* device [N,H,W,3] f32 camera-space maps, both or neither */
+    int32_t H, W;                         /* H W < 2^24 */
+    int32_t radius;                       /* window half-width of the correspondence search, 0 .. 32 */
+    int32_t reserved;
+    double fx, fy, cx, cy;                /* the maps' intrinsics */
+    double robust_delta;                  /* Huber delta on the residual, > 0 */
+    double w_sparse, w_dense;             /* >= 0 */
+    double dist_thresh;                   /* > 0 */
+    double normal_thresh;                 /* cosine */
+    double depth_min, depth_max;          /* a point is valid if depth_min < z < depth_max */
+    double min_trace;                     /* a pair is active iff trace(R_i^T R_j) > min_trace; -inf = always */
+    void *workspace;                      /* device, at least nof_pose_graph_workspace_bytes(N, P, M, H, W) */
+    size_t workspace_bytes;
+    double *poses_out;                    /* device [N,16] f64 */
+    double *history;                      /* device [n_outer+1,4] f64 */
+    /* debug outputs, NULL = not written */
+    double *iter_poses;                   /* device [n_outer+1,N,16] f64: the poses of every linearisation, then the final ones */
+    double *dbg_A;                        /* device [n_outer,6N,6N] f64 */
+    double *dbg_g;                        /* device [n_outer,6N] f64 */
+    double *dbg_delta;                    /* device [n_outer,6N] f64 */
+    int32_t *dense_index;                 /* device [n_outer,N,N,H W] i32, filled with -1 by the caller: entry (target i,
+                                             source j, source pixel) = the chosen target pixel, written for active pairs */
+} nof_pose_graph_desc;
+
+/* Working poses, valid counts, per-(pair, chunk) partial sums, A, g and the history sums. H = W = 0
+ * without a dense term. 0 for arguments out of range. */
+size_t nof_pose_graph_workspace_bytes(int32_t N, int32_t P, int64_t M, int32_t H, int32_t W);
+
+/* 1 + (n_outer + 1) x at most 4 launches on `stream`; nothing is allocated or read back. The whole
+ * descriptor is validated before the first HIP call: NOF_EINVAL with nof_last_error naming the field
+ * (N, n_outer, n_inner, P, M, neither term given, robust_delta, a NULL input or output, one map of two,
+ * H, W, radius, dist_thresh, a weight below 0, a NaN threshold or intrinsic, workspace_bytes). */
+int nof_pose_graph_optimize(const nof_pose_graph_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
