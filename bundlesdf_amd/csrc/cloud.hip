@@ -16,7 +16,7 @@
 //  k_label           core -> root (= the cluster's lowest core index, where
 //                    sklearn starts it); border -> root of its lowest-index
 //                    core neighbour; noise -> -1.
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
@@ -60,27 +60,11 @@ __global__ __launch_bounds__(256) void k_knn_mean_dist(const double *__restrict_
     if (lane == 0) out[q] = (s + (double)(ke - below) * sqrt(t)) / (double)ke;
 }
 
-struct Grid {
-    double org[3], eps, eps2;
-    int32_t dims[3];
-    const int32_t *start;
-    const double *cpts;
-    const int32_t *ids;
-};
-
-__device__ __forceinline__ void cell_of(const Grid &g, const double *p, int c[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double x = floor((p[a] - g.org[a]) / g.eps);
-        c[a] = x < 0 ? 0 : (x > g.dims[a] - 1 ? g.dims[a] - 1 : (int)x);
-    }
-}
-
-// Visit every grid point j with |p_j - p| <= eps (p itself included): f(j).
+// Visit every grid point j with |p_j - p| <= eps (p itself included): f(j). The grid's cell edge is eps.
 template <typename F>
-__device__ __forceinline__ void for_neighbours(const Grid &g, const double *p, F f) {
+__device__ __forceinline__ void for_neighbours(const PointGrid &g, const double *p, F f) {
     int c[3];
-    cell_of(g, p, c);
+    grid_cell(g, p, c);
     for (int z = c[2] - 1; z <= c[2] + 1; ++z) {
         if (z < 0 || z >= g.dims[2]) continue;
         for (int y = c[1] - 1; y <= c[1] + 1; ++y) {
@@ -91,14 +75,14 @@ __device__ __forceinline__ void for_neighbours(const Grid &g, const double *p, F
                 for (int32_t i = g.start[cell]; i < g.start[cell + 1]; ++i) {
                     const double *q = g.cpts + (size_t)i * 3;
                     const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
-                    if (sqrt((dx * dx + dy * dy) + dz * dz) <= g.eps) f(g.ids[i]);
+                    if (sqrt((dx * dx + dy * dy) + dz * dz) <= g.cell) f(g.ids[i]);
                 }
             }
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_core_count(Grid g, const double *__restrict__ pts, int32_t n,
+__global__ __launch_bounds__(256) void k_core_count(PointGrid g, const double *__restrict__ pts, int32_t n,
                                                     int32_t min_samples, uint8_t *__restrict__ core,
                                                     int32_t *__restrict__ parent) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -109,16 +93,7 @@ __global__ __launch_bounds__(256) void k_core_count(Grid g, const double *__rest
     parent[i] = i;
 }
 
-__device__ __forceinline__ int find_root(const int32_t *parent, int i) {
-    int p = parent[i];
-    while (p != i) {
-        i = p;
-        p = parent[i];
-    }
-    return i;
-}
-
-__global__ __launch_bounds__(256) void k_hook(Grid g, const double *__restrict__ pts, int32_t n,
+__global__ __launch_bounds__(256) void k_hook(PointGrid g, const double *__restrict__ pts, int32_t n,
                                               const uint8_t *__restrict__ core, int32_t *parent,
                                               int32_t *__restrict__ changed) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -126,7 +101,7 @@ __global__ __launch_bounds__(256) void k_hook(Grid g, const double *__restrict__
     int hooked = 0;
     for_neighbours(g, pts + (size_t)i * 3, [&](int j) {
         if (j == i || !core[j]) return;
-        const int ri = find_root(parent, i), rj = find_root(parent, j);
+        const int ri = uf_find(parent, i), rj = uf_find(parent, j);
         if (ri == rj) return;
         const int hi = ri > rj ? ri : rj, lo = ri > rj ? rj : ri;
         atomicMin(&parent[hi], lo);
@@ -138,10 +113,10 @@ __global__ __launch_bounds__(256) void k_hook(Grid g, const double *__restrict__
 __global__ __launch_bounds__(256) void k_jump(int32_t n, int32_t *parent) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    parent[i] = find_root(parent, i);
+    uf_compress(parent, i);
 }
 
-__global__ __launch_bounds__(256) void k_label(Grid g, const double *__restrict__ pts, int32_t n,
+__global__ __launch_bounds__(256) void k_label(PointGrid g, const double *__restrict__ pts, int32_t n,
                                                const uint8_t *__restrict__ core, const int32_t *__restrict__ parent,
                                                int32_t *__restrict__ labels) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -153,8 +128,6 @@ __global__ __launch_bounds__(256) void k_label(Grid g, const double *__restrict_
     });
     labels[i] = best == 0x7fffffff ? -1 : parent[best];
 }
-
-static size_t align256c(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace nof
 
@@ -172,8 +145,8 @@ int nof_knn_mean_dist(const double *points, int32_t n, int32_t k, double *mean_d
 }
 
 size_t nof_dbscan_workspace_bytes(int32_t n, int64_t n_cells) {
-    return align256c((size_t)(n_cells + 1) * 4) + align256c((size_t)n * 24) + align256c((size_t)n * 4) * 2 +
-           align256c((size_t)n) + 256 + nof_point_grid_workspace_bytes(n_cells);
+    return align256((size_t)(n_cells + 1) * 4) + align256((size_t)n * 24) + align256((size_t)n * 4) * 2 +
+           align256((size_t)n) + 256 + nof_point_grid_workspace_bytes(n_cells);
 }
 
 int nof_dbscan(const double *points, int32_t n, double eps, int32_t min_samples, const double *origin,
@@ -186,24 +159,20 @@ int nof_dbscan(const double *points, int32_t n, double eps, int32_t min_samples,
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    Grid g;
-    g.start = (int32_t *)ws;
-    ws += align256c((size_t)(nc + 1) * 4);
-    g.cpts = (double *)ws;
-    ws += align256c((size_t)n * 24);
-    g.ids = (int32_t *)ws;
-    ws += align256c((size_t)n * 4);
+    int32_t *start = (int32_t *)ws;
+    ws += align256((size_t)(nc + 1) * 4);
+    double *cpts = (double *)ws;
+    ws += align256((size_t)n * 24);
+    int32_t *ids = (int32_t *)ws;
+    ws += align256((size_t)n * 4);
     int32_t *parent = (int32_t *)ws;
-    ws += align256c((size_t)n * 4);
+    ws += align256((size_t)n * 4);
     uint8_t *core = (uint8_t *)ws;
-    ws += align256c((size_t)n);
+    ws += align256((size_t)n);
     int32_t *changed = (int32_t *)ws;
     ws += 256;
-    for (int a = 0; a < 3; ++a) { g.org[a] = origin[a]; g.dims[a] = dims[a]; }
-    g.eps = eps;
-    g.eps2 = eps * eps;
-    int rc = nof_point_grid_build(points, n, origin, dims, eps, (int32_t *)g.start, (double *)g.cpts,
-                                  (int32_t *)g.ids, ws, stream);
+    const PointGrid g = point_grid(origin, dims, eps, start, cpts, ids);     // cell edge = eps
+    int rc = nof_point_grid_build(points, n, origin, dims, eps, start, cpts, ids, ws, stream);
     if (rc) return rc;
     const unsigned nb = div_up(n, 256);
     hipLaunchKernelGGL(k_core_count, dim3(nb), dim3(256), 0, s, g, points, n, min_samples, core, parent);

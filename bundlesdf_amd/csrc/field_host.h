@@ -19,7 +19,6 @@ inline int cu_count() {
 inline int tile_blocks(int64_t n, int per_block, int n_cu, int per_cu) {
     return (int)std::min<int64_t>((n + per_block - 1) / per_block, (int64_t)n_cu * per_cu);
 }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }   // workspace sections
 
 // f(tag) with the kernels' template types (TM the MLP's element type, TT the table's), and one launch of
 // the kernel template K<TM, TT> through it; `lds` may name TM

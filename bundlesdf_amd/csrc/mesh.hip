@@ -23,7 +23,7 @@
 // wave has just read (DESIGN.md records the choice).
 #include <cmath>
 
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
@@ -171,24 +171,13 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_faces(int n1, int n2, int P, co
     }
 }
 
-// Root of v: labels never exceed their index and only ever decrease, so the walk strictly descends
-// (at most v steps) even while other lanes hook and compress; a label outside [0, r) ends it.
-__device__ __forceinline__ int32_t cc_find(const int32_t *labels, int32_t v) {
-    int32_t r = v;
-    for (;;) {
-        const int32_t l = __hip_atomic_load(labels + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (l >= r || l < 0) return r;
-        r = l;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_cc_hook(const int32_t *__restrict__ faces, int64_t F, int64_t V, int32_t *labels,
                                                  int32_t *changed) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     const int32_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
     if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) return;   // not a face of this mesh
-    const int32_t r[3] = {cc_find(labels, a), cc_find(labels, b), cc_find(labels, c)};
+    const int32_t r[3] = {uf_find(labels, a), uf_find(labels, b), uf_find(labels, c)};
     const int32_t m = min(r[0], min(r[1], r[2]));
     bool lowered = false;
 #pragma unroll
@@ -200,8 +189,7 @@ __global__ __launch_bounds__(256) void k_cc_hook(const int32_t *__restrict__ fac
 __global__ __launch_bounds__(256) void k_cc_compress(int64_t V, int32_t *labels) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
-    const int32_t r = cc_find(labels, (int32_t)v);
-    if (r != (int32_t)v) __hip_atomic_store(labels + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uf_compress(labels, (int32_t)v);
 }
 
 static int mc_shape(const char *fn, int32_t n0, int32_t n1, int32_t n2, int64_t *points) {

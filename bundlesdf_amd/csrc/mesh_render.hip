@@ -2,16 +2,12 @@
 // poses, the device counterpart of the reference's pyrender pass (offscreen_renderer.py:
 // ModelRendererOffscreen). Three kernels on one stream, nothing read back:
 //
-//  k_mesh_setup   one lane per (pose, face). project_face is k_raster's arithmetic (texture.hip):
-//                 X = ((R0 x + R1 y) + R2 w) + t in f64, a vertex at Z <= znear drops the face,
-//                 u = fx X / Z + cx, area = (u1-u0)(v2-v0) - (u2-u0)(v1-v0), area == 0 drops it, the
-//                 bounding box is ceil(min) .. floor(max) clamped to the image. A box of at most
-//                 small_max_pixels pixels is walked by the lane itself (cover: the edge functions
-//                 over the area, all three >= 0, zi = 1 / ((e0/z0 + e1/z1) + e2/z2), zi <= zfar,
-//                 atomicMin of (bits of (float)zi << 32 | face) into the pose's z-buffer). Any other
-//                 face is appended to the list of large faces: one counter increment per wave
-//                 (ballot, prefix count, one atomicAdd by the first listing lane). The list has a
-//                 slot for every (pose, face).
+//  k_mesh_setup   one lane per (pose, face): project_face (raster.h holds the definition of the
+//                 projection, cull, coverage, depth and key, shared with nof_raster_faces). A box of
+//                 at most small_max_pixels pixels is walked by the lane itself (splat into the pose's
+//                 z-buffer). Any other face is appended to the list of large faces: one counter
+//                 increment per wave (ballot, prefix count, one atomicAdd by the first listing lane).
+//                 The list has a slot for every (pose, face).
 //  k_mesh_large   one wave per list entry, a fixed grid striding over the list (the count is read
 //                 from device memory). The 64 lanes take consecutive pixels of the bounding box in
 //                 row-major order, so a wave's atomics land on neighbouring addresses and a
@@ -24,7 +20,7 @@
 //                   3. n = (w0 n_0 + w1 n_1) + w2 n_2 per component with vertex normals (f32 widened
 //                      to f64), else the face normal a x b, a = p1 - p0, b = p2 - p0 (object frame,
 //                      f64): (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x).
-//                   4. camera frame: m_r = (R_r0 n_x + R_r1 n_y) + R_r2 n_z; l = sqrt((m_x m_x +
+//                   4. camera frame: m = xform_dir(T, n), the rotation alone; l = sqrt((m_x m_x +
 //                      m_y m_y) + m_z m_z); l > 0: m = m / l (a zero normal stays zero).
 //                   5. pixel ray d = ((px - cx) / fx, (py - cy) / fy, 1) / sqrt((d_x d_x + d_y d_y) + 1);
 //                      c = (m_x d_x + m_y d_y) + m_z d_z; c > 0: m = -m. normal = (float)m.
@@ -38,78 +34,15 @@
 //
 // All of it is IEEE f64 + - * / sqrt in the stated order with contraction off; tests/mesh_render_oracle.py
 // restates steps 2-8 in numpy and the z-buffer is oracle/texture.py's raster.
-#include <cmath>
-
-#include "nof_device.h"
+#include "raster.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
 
-struct MeshCam {
-    double fx, fy, cx, cy;
-};
-
-struct Tri {
-    double u[3], v[3], z[3], area;
-    int u0, u1, v0, v1;        // clamped bounding box; empty when u1 < u0 or v1 < v0
-};
-
-// k_raster's projection and cull. T: the pose's 16 doubles (device). False: the face is dropped.
-__device__ __forceinline__ bool project_face(const float *__restrict__ V, const int64_t *__restrict__ F, int64_t f,
-                                             const double *__restrict__ T, const MeshCam &c, int H, int W,
-                                             double znear, Tri &t) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float *p = V + F[f * 3 + k] * 3;
-        const double x = p[0], y = p[1], w = p[2];
-        const double X = ((T[0] * x + T[1] * y) + T[2] * w) + T[3];
-        const double Y = ((T[4] * x + T[5] * y) + T[6] * w) + T[7];
-        const double Z = ((T[8] * x + T[9] * y) + T[10] * w) + T[11];
-        if (!(Z > znear)) return false;      // no near-plane clipping: faces crossing it are dropped
-        t.z[k] = Z;
-        t.u[k] = c.fx * X / Z + c.cx;
-        t.v[k] = c.fy * Y / Z + c.cy;
-    }
-    const double *u = t.u, *v = t.v;
-    t.area = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
-    if (t.area == 0.0) return false;
-    // the comparisons are made in f64 before the cast: a projection far outside the image (or a
-    // non-finite one) must not reach an out-of-range double -> int conversion
-    const double lu = ceil(fmin(fmin(u[0], u[1]), u[2])), hu = floor(fmax(fmax(u[0], u[1]), u[2]));
-    const double lv = ceil(fmin(fmin(v[0], v[1]), v[2])), hv = floor(fmax(fmax(v[0], v[1]), v[2]));
-    if (!(lu <= (double)(W - 1)) || !(hu >= 0.0) || !(lv <= (double)(H - 1)) || !(hv >= 0.0)) return false;
-    t.u0 = lu < 0.0 ? 0 : (int)lu;
-    t.v0 = lv < 0.0 ? 0 : (int)lv;
-    t.u1 = hu > (double)(W - 1) ? W - 1 : (int)hu;
-    t.v1 = hv > (double)(H - 1) ? H - 1 : (int)hv;
-    return true;
-}
-
-// k_raster's coverage and depth at pixel centre (px, py). False: not covered or beyond zfar.
-__device__ __forceinline__ bool cover(const Tri &t, int px, int py, double zfar, double e[3], double &zi) {
-    const double X = px, Y = py;
-    const double *u = t.u, *v = t.v;
-    // barycentric weights of vertex k = edge function of the opposite edge / area
-    e[0] = ((u[2] - u[1]) * (Y - v[1]) - (v[2] - v[1]) * (X - u[1])) / t.area;
-    e[1] = ((u[0] - u[2]) * (Y - v[2]) - (v[0] - v[2]) * (X - u[2])) / t.area;
-    e[2] = ((u[1] - u[0]) * (Y - v[0]) - (v[1] - v[0]) * (X - u[0])) / t.area;
-    if (e[0] < 0.0 || e[1] < 0.0 || e[2] < 0.0) return false;
-    zi = 1.0 / ((e[0] / t.z[0] + e[1] / t.z[1]) + e[2] / t.z[2]);
-    return zi <= zfar;
-}
-
-__device__ __forceinline__ void splat(const Tri &t, int px, int py, double zfar, uint32_t f, int W,
-                                      unsigned long long *__restrict__ zb) {
-    double e[3], zi;
-    if (!cover(t, px, py, zfar, e, zi)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint((float)zi) << 32) | (unsigned long long)f;
-    atomicMin(&zb[(size_t)py * W + px], key);
-}
-
 __global__ __launch_bounds__(256) void k_mesh_setup(const float *__restrict__ V, const int64_t *__restrict__ F,
                                                     int64_t nF, const double *__restrict__ poses, int64_t n_items,
-                                                    MeshCam c, int H, int W, double znear, double zfar,
+                                                    Pinhole c, int H, int W, double znear, double zfar,
                                                     int small_max, unsigned long long *__restrict__ zbuf,
                                                     unsigned long long *__restrict__ list,
                                                     unsigned int *__restrict__ n_large) {
@@ -141,7 +74,7 @@ __global__ __launch_bounds__(256) void k_mesh_setup(const float *__restrict__ V,
 }
 
 __global__ __launch_bounds__(256) void k_mesh_large(const float *__restrict__ V, const int64_t *__restrict__ F,
-                                                    const double *__restrict__ poses, MeshCam c, int H, int W,
+                                                    const double *__restrict__ poses, Pinhole c, int H, int W,
                                                     double znear, double zfar, unsigned long long *__restrict__ zbuf,
                                                     const unsigned long long *__restrict__ list,
                                                     const unsigned int *__restrict__ n_large) {
@@ -177,7 +110,7 @@ __device__ __forceinline__ double mix3(const double w[3], double a, double b, do
 }
 
 __global__ __launch_bounds__(256) void k_mesh_shade(const float *__restrict__ V, const int64_t *__restrict__ F,
-                                                    const double *__restrict__ poses, int64_t n_pixels, MeshCam c,
+                                                    const double *__restrict__ poses, int64_t n_pixels, Pinhole c,
                                                     int H, int W, double znear, double zfar, MeshShade s,
                                                     const unsigned long long *__restrict__ zbuf,
                                                     float *__restrict__ depth, int32_t *__restrict__ face,
@@ -216,7 +149,7 @@ __global__ __launch_bounds__(256) void k_mesh_shade(const float *__restrict__ V,
             n[2] = a[0] * d[1] - a[1] * d[0];
         }
         double m[3];
-        for (int r = 0; r < 3; ++r) m[r] = (T[4 * r] * n[0] + T[4 * r + 1] * n[1]) + T[4 * r + 2] * n[2];
+        xform_dir(T, n[0], n[1], n[2], m);
         const double l = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
         if (l > 0.0) {
             m[0] = m[0] / l;
@@ -311,7 +244,7 @@ int nof_render_mesh(const nof_mesh_render_desc *d, void *stream) {
         {d->rgb, "rgb", true}, {d->normal, "normal", true}};
     for (const auto &a : ptrs)
         if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
-    const MeshCam c = {d->K[0], d->K[4], d->K[2], d->K[5]};
+    const Pinhole c = {d->K[0], d->K[4], d->K[2], d->K[5]};
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_pixels = (int64_t)d->B * d->H * d->W, n_items = (int64_t)d->B * d->n_faces;
     unsigned int *n_large = (unsigned int *)d->workspace;

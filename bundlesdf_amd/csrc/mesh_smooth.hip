@@ -17,7 +17,7 @@
 //  k_vertex_normals   one thread per vertex: the unnormalised (v1 - v0) x (v2 - v0)
 //                     of its faces (vertex -> face CSR, ascending face index) added
 //                     in that order, then divided by the sum's length.
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
@@ -62,8 +62,8 @@ __global__ __launch_bounds__(256) void k_laplacian_step(const double *__restrict
 
 __global__ __launch_bounds__(256) void k_mesh_volume(const double *__restrict__ v, const int32_t *__restrict__ faces,
                                                      int64_t F, double *__restrict__ partial) {
-    __shared__ double wave_sum[4];
-    double acc = 0.0;
+    __shared__ double wave_sum[4][1];
+    double acc[1] = {0.0};
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += stride) {
         const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
@@ -71,13 +71,9 @@ __global__ __launch_bounds__(256) void k_mesh_volume(const double *__restrict__ 
         const double x1 = v[b * 3], y1 = v[b * 3 + 1], z1 = v[b * 3 + 2];
         const double x2 = v[c * 3], y2 = v[c * 3 + 1], z2 = v[c * 3 + 2];
         const double cx = y1 * z2 - z1 * y2, cy = z1 * x2 - x1 * z2, cz = x1 * y2 - y1 * x2;
-        acc += (x0 * cx + y0 * cy) + z0 * cz;
+        acc[0] += (x0 * cx + y0 * cy) + z0 * cz;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+    block_sum<1>(acc, wave_sum, partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_mesh_volume_final(const double *__restrict__ partial, int32_t n_blocks,

@@ -19,19 +19,11 @@
 //                  butterfly over the wave, waves added in order, one partial row
 //                  per block; k_corr_final adds the rows in block order. No
 //                  floating-point atomics: two runs give the same bits.
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
-
-struct NearestGrid {
-    double org[3], cell, max_dist;
-    int32_t dims[3];
-    const int32_t *start;
-    const double *cpts;
-    const int32_t *ids;
-};
 
 // Lower bound of |p_a - q_a| over the points p whose cell index along an axis is
 // beyond the face at org + k cell, given g = the query's signed distance to that
@@ -44,25 +36,16 @@ __device__ __forceinline__ double face_gap(double g, double magnitude) {
     return s > 0.0 ? s : 0.0;
 }
 
-__global__ __launch_bounds__(256) void k_nearest(NearestGrid g, const double *__restrict__ queries, int32_t Q,
-                                                 const double *__restrict__ xforms, int32_t *__restrict__ index,
-                                                 double *__restrict__ dist) {
+__global__ __launch_bounds__(256) void k_nearest(PointGrid g, double max_dist, const double *__restrict__ queries,
+                                                 int32_t Q, const double *__restrict__ xforms,
+                                                 int32_t *__restrict__ index, double *__restrict__ dist) {
     const int32_t qi = blockIdx.x * 256 + threadIdx.x;
     if (qi >= Q) return;
     const int32_t b = blockIdx.y;
     double q[3] = {queries[(size_t)qi * 3], queries[(size_t)qi * 3 + 1], queries[(size_t)qi * 3 + 2]};
-    if (xforms) {
-        const double *T = xforms + (size_t)b * 16;
-        const double x = q[0], y = q[1], z = q[2];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) q[a] = ((T[a * 4] * x + T[a * 4 + 1] * y) + T[a * 4 + 2] * z) + T[a * 4 + 3];
-    }
+    if (xforms) xform_point(xforms + (size_t)b * 16, q[0], q[1], q[2], q);
     int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double x = floor((q[a] - g.org[a]) / g.cell);
-        c[a] = !(x >= 0) ? 0 : (x > g.dims[a] - 1 ? g.dims[a] - 1 : (int)x);   // NaN -> cell 0
-    }
+    grid_cell(g, q, c);
     double best = __longlong_as_double(0x7ff0000000000000ll);
     int32_t bi = -1;
     auto scan = [&](int64_t first, int64_t last) {   // the points of cells first..last (one x-row piece)
@@ -112,10 +95,10 @@ __global__ __launch_bounds__(256) void k_nearest(NearestGrid g, const double *__
                 gap = f < gap ? f : gap;
             }
         }
-        if (covered || best <= gap * gap || (g.max_dist > 0 && gap > g.max_dist)) break;
+        if (covered || best <= gap * gap || (max_dist > 0 && gap > max_dist)) break;
     }
     double d = sqrt(best);
-    if (bi < 0 || (g.max_dist > 0 && d > g.max_dist)) {
+    if (bi < 0 || (max_dist > 0 && d > max_dist)) {
         bi = -1;
         d = __longlong_as_double(0x7ff0000000000000ll);
     }
@@ -123,63 +106,38 @@ __global__ __launch_bounds__(256) void k_nearest(NearestGrid g, const double *__
     dist[(size_t)b * Q + qi] = d;
 }
 
-constexpr int MOMENTS = 17;
 constexpr int MOMENT_BLOCKS = 1024;
 
 __global__ __launch_bounds__(256) void k_corr_moments(const double *__restrict__ src, int32_t n,
                                                       const double *__restrict__ xform, const double *__restrict__ tgt,
                                                       int32_t m, const int32_t *__restrict__ index,
                                                       const double *__restrict__ dist, double *__restrict__ partial) {
-    __shared__ double wave_sum[4][MOMENTS];
+    __shared__ double wave_sum[4][RIGID_SUMS];
     double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     if (xform) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) T[k] = xform[k];
     }
-    double acc[MOMENTS];
+    double acc[RIGID_SUMS];
 #pragma unroll
-    for (int k = 0; k < MOMENTS; ++k) acc[k] = 0.0;
+    for (int k = 0; k < RIGID_SUMS; ++k) acc[k] = 0.0;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const int32_t j = index[i];
         if (j < 0 || j >= m) continue;
-        const double x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
-        double p[3], t[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            p[a] = ((T[a * 4] * x + T[a * 4 + 1] * y) + T[a * 4 + 2] * z) + T[a * 4 + 3];
-            t[a] = tgt[(size_t)j * 3 + a];
-        }
-        acc[0] += 1.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            acc[1 + a] += p[a];
-            acc[4 + a] += t[a];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[7 + a * 3 + c] += p[a] * t[c];
-        }
+        double p[3];
+        xform_point(T, src[i * 3], src[i * 3 + 1], src[i * 3 + 2], p);
+        rigid_moments_add(acc, p, tgt + (size_t)j * 3);
         acc[16] += dist[i] * dist[i];
     }
-#pragma unroll
-    for (int k = 0; k < MOMENTS; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < MOMENTS; ++k) wave_sum[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < MOMENTS)
-        partial[(size_t)blockIdx.x * MOMENTS + threadIdx.x] =
-            ((wave_sum[0][threadIdx.x] + wave_sum[1][threadIdx.x]) + wave_sum[2][threadIdx.x]) + wave_sum[3][threadIdx.x];
+    block_sum<RIGID_SUMS>(acc, wave_sum, partial + (size_t)blockIdx.x * RIGID_SUMS);
 }
 
 __global__ __launch_bounds__(64) void k_corr_final(const double *__restrict__ partial, int32_t n_blocks,
                                                    double *__restrict__ out) {
-    if (threadIdx.x >= MOMENTS) return;
+    if (threadIdx.x >= RIGID_SUMS) return;
     double s = 0.0;
-    for (int32_t b = 0; b < n_blocks; ++b) s += partial[(size_t)b * MOMENTS + threadIdx.x];
+    for (int32_t b = 0; b < n_blocks; ++b) s += partial[(size_t)b * RIGID_SUMS + threadIdx.x];
     out[threadIdx.x] = s;
 }
 
@@ -209,22 +167,13 @@ int nof_nearest_points(const double *queries, int32_t Q, const double *xforms, i
     if (n == 0) return set_error(NOF_EINVAL, "nearest_points: empty cloud with %d queries", Q);
     if (!queries || !cell_points || !cell_ids || !index || !dist)
         return set_error(NOF_EINVAL, "nearest_points: NULL input/output pointer (cell_ids is required)");
-    NearestGrid g;
-    for (int a = 0; a < 3; ++a) {
-        g.org[a] = origin[a];
-        g.dims[a] = dims[a];
-    }
-    g.cell = cell;
-    g.max_dist = max_dist;
-    g.start = cell_start;
-    g.cpts = cell_points;
-    g.ids = cell_ids;
-    hipLaunchKernelGGL(k_nearest, dim3(div_up(Q, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, g, queries, Q,
-                       xforms, index, dist);
+    hipLaunchKernelGGL(k_nearest, dim3(div_up(Q, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       point_grid(origin, dims, cell, cell_start, cell_points, cell_ids), max_dist, queries, Q, xforms,
+                       index, dist);
     return check_launch("nearest_points");
 }
 
-size_t nof_nearest_workspace_bytes(int32_t n) { return (size_t)moment_blocks(n) * MOMENTS * sizeof(double); }
+size_t nof_nearest_workspace_bytes(int32_t n) { return (size_t)moment_blocks(n) * RIGID_SUMS * sizeof(double); }
 
 int nof_correspondence_moments(const double *source, int32_t n, const double *xform, const double *target, int32_t m,
                                const int32_t *index, const double *dist, double *sums, void *workspace, void *stream) {

@@ -80,5 +80,7 @@ __device__ __forceinline__ void atomic_add_f32(float *addr, float v) {
 }
 
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+// Workspace parts start on 256-byte boundaries.
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace nof

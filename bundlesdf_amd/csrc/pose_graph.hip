@@ -15,7 +15,8 @@
 //    (E[r][0] T[0][c] + E[r][1] T[1][c]) + E[r][2] T[2][c], plus E[r][3] for c = 3. A fixed frame is
 //    a constant: its pose comes back bit for bit and its rows and columns of the system are zero.
 //  Point transform. (T p)_k = ((T[k][0] px + T[k][1] py) + T[k][2] pz) + T[k][3]; a normal is
-//    rotated the same way without the last term.
+//    rotated the same way without the last term (xform_point / xform_dir of geom_device.h, which also
+//    holds the block sum of the kernels below and pair_rows).
 //  Huber. For a squared residual e and delta: e <= delta^2: rho = e, rho' = 1; else s = sqrt(e),
 //    rho = 2 s delta - delta^2, rho' = delta / s.
 //  Sparse row of pair (i, j), match (pa, pb), weight wt (a row with wt == 0 does not exist).
@@ -60,7 +61,7 @@
 //  k_pg_solve     one block: PCG on the explicit A, the Lie update, the history row.
 #include <math.h>
 
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
@@ -79,11 +80,6 @@ constexpr double PG_EPS = 1e-6;         // FLOAT_EPSILON of the reference's PCG 
 // index of (r, c), r <= c, in the 21 entries of a symmetric 6x6
 __host__ __device__ constexpr int pg_sym(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }
 __device__ __forceinline__ int pg_sym_any(int r, int c) { return r <= c ? pg_sym(r, c) : pg_sym(c, r); }
-
-__device__ __forceinline__ void pg_xform(const double *__restrict__ T, double x, double y, double z, double (&o)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = ((T[k * 4] * x + T[k * 4 + 1] * y) + T[k * 4 + 2] * z) + T[k * 4 + 3];
-}
 
 __device__ __forceinline__ void pg_huber(double e, double delta, double &rho, double &drho) {
     if (e <= delta * delta) {
@@ -105,36 +101,6 @@ __device__ __forceinline__ void pg_jac(const double (&a)[3], double (&J)[3][6]) 
     for (int k = 0; k < 3; ++k)
 #pragma unroll
         for (int c = 0; c < 3; ++c) J[k][3 + c] = k == c ? 1.0 : 0.0;
-}
-
-// The pair's rows [s, s + n), both ends clamped into [0, M] whatever pair_start holds.
-__device__ __forceinline__ void pg_pair_rows(const int32_t *__restrict__ pair_start, int32_t p, int64_t M, int64_t &s,
-                                             int32_t &n) {
-    int64_t a = pair_start[p], b = pair_start[p + 1];
-    a = a < 0 ? 0 : (a > M ? M : a);
-    b = b < a ? a : (b > M ? M : b);
-    s = a;
-    n = (int32_t)(b - a);
-}
-
-// Sum of K per-lane values over the 256 threads of a block: butterfly in the wave, the four waves
-// in order; thread k < K ends with total k in `out`. wave_sum is [4][K] of LDS.
-template <int K>
-__device__ __forceinline__ void pg_block_sum(double (&acc)[K], double (*wave_sum)[K], double *__restrict__ out) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) wave_sum[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < K) {
-        const int k = threadIdx.x;
-        out[k] = ((wave_sum[0][k] + wave_sum[1][k]) + wave_sum[2][k]) + wave_sum[3][k];
-    }
 }
 
 __device__ __forceinline__ bool pg_valid(const float *__restrict__ p, const float *__restrict__ n, double depth_min,
@@ -183,7 +149,7 @@ __global__ __launch_bounds__(256) void k_pg_sparse(const int32_t *__restrict__ p
     }
     int64_t s;
     int32_t n;
-    pg_pair_rows(pair_start, p, M, s, n);
+    pair_rows(pair_start, p, M, s, n);
     const double *Ti = T + (size_t)i * 16, *Tj = T + (size_t)j * 16;
     double acc[PG_SP];
 #pragma unroll
@@ -196,8 +162,8 @@ __global__ __launch_bounds__(256) void k_pg_sparse(const int32_t *__restrict__ p
         const double wt = weight ? weight[m] : 1.0;
         if (wt == 0.0) continue;
         double a[3], b[3], r[3];
-        pg_xform(Ti, pts_a[m * 3], pts_a[m * 3 + 1], pts_a[m * 3 + 2], a);
-        pg_xform(Tj, pts_b[m * 3], pts_b[m * 3 + 1], pts_b[m * 3 + 2], b);
+        xform_point(Ti, pts_a[m * 3], pts_a[m * 3 + 1], pts_a[m * 3 + 2], a);
+        xform_point(Tj, pts_b[m * 3], pts_b[m * 3 + 1], pts_b[m * 3 + 2], b);
 #pragma unroll
         for (int k = 0; k < 3; ++k) r[k] = a[k] - b[k];
         const double e = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
@@ -223,7 +189,7 @@ __global__ __launch_bounds__(256) void k_pg_sparse(const int32_t *__restrict__ p
         acc[90] += w0 * rho;
         acc[91] += 1.0;
     }
-    pg_block_sum<PG_SP>(acc, wave_sum, out);
+    block_sum<PG_SP>(acc, wave_sum, out);
 }
 
 struct PgDense {
@@ -283,9 +249,8 @@ __global__ __launch_bounds__(256) void k_pg_dense(PgDense d, const double *__res
         if (pg_valid(Ps + (size_t)s * 3, Ns + (size_t)s * 3, d.depth_min, d.depth_max)) {
             const double nx = (double)Ns[(size_t)s * 3], ny = (double)Ns[(size_t)s * 3 + 1], nz = (double)Ns[(size_t)s * 3 + 2];
             double nq[3];
-            pg_xform(rel, px, py, pz, q);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) nq[k] = (rel[k * 4] * nx + rel[k * 4 + 1] * ny) + rel[k * 4 + 2] * nz;
+            xform_point(rel, px, py, pz, q);
+            xform_dir(rel, nx, ny, nz, nq);
             if (q[2] > 0.0) {
                 const double u = (d.fx * q[0]) / q[2] + d.cx, v = (d.fy * q[1]) / q[2] + d.cy;
                 if (fabs(u) < 1e9 && fabs(v) < 1e9) {                    // false for NaN
@@ -325,9 +290,8 @@ __global__ __launch_bounds__(256) void k_pg_dense(PgDense d, const double *__res
         pg_huber(res * res, d.delta, rho, drho);
         const double w = d.w_dense * drho;
         double a[3], u[6];
-        pg_xform(Tj, px, py, pz, a);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) u[3 + k] = (Ti[k * 4] * ntx + Ti[k * 4 + 1] * nty) + Ti[k * 4 + 2] * ntz;
+        xform_point(Tj, px, py, pz, a);
+        xform_dir(Ti, ntx, nty, ntz, u + 3);
         u[0] = a[1] * u[5] - a[2] * u[4];
         u[1] = a[2] * u[3] - a[0] * u[5];
         u[2] = a[0] * u[4] - a[1] * u[3];
@@ -341,7 +305,7 @@ __global__ __launch_bounds__(256) void k_pg_dense(PgDense d, const double *__res
         acc[27] += d.w_dense * rho;
         acc[28] += 1.0;
     }
-    pg_block_sum<PG_DN>(acc, wave_sum, out);
+    block_sum<PG_DN>(acc, wave_sum, out);
 }
 
 struct PgAssemble {
@@ -375,7 +339,7 @@ __global__ __launch_bounds__(256) void k_pg_assemble(PgAssemble d, int32_t total
                     acc[1] += q[27];
                     acc[3] += q[28];
                 }
-        pg_block_sum<4>(acc, wave_sum, totals);
+        block_sum<4>(acc, wave_sum, totals);
         return;
     }
     const int32_t bi = blockIdx.x / N, bj = blockIdx.x % N;
@@ -569,8 +533,6 @@ struct PgPlan {
     size_t off_cnt, off_sp, off_dn, off_A, off_g, off_totals, bytes;
 };
 
-static size_t pg_align(size_t x) { return (x + 255) / 256 * 256; }
-
 // The workspace: T [N,16] f64 | cnt [N] i32 | sp_part [P, sp_chunks, 92] f64 | dn_part [N (N - 1) / 2,
 // dn_chunks, 29] f64 | A [6N,6N] f64 | g [6N] f64 | totals [4] f64, each part aligned to 256 bytes.
 static PgPlan pg_plan(int32_t N, int32_t P, int64_t M, int32_t H, int32_t W) {
@@ -580,19 +542,19 @@ static PgPlan pg_plan(int32_t N, int32_t P, int64_t M, int32_t H, int32_t W) {
     const uint64_t tiles = (H > 0 && W > 0) ? div_up((uint64_t)H * (uint64_t)W, PG_TILE) : 0;
     pl.dn_chunks = (int32_t)(tiles > PG_DN_MAX_CHUNKS ? PG_DN_MAX_CHUNKS : tiles);
     const size_t n = 6 * (size_t)N;
-    size_t at = pg_align((size_t)N * 16 * sizeof(double));
+    size_t at = align256((size_t)N * 16 * sizeof(double));
     pl.off_cnt = at;
-    at += pg_align((size_t)N * sizeof(int32_t));
+    at += align256((size_t)N * sizeof(int32_t));
     pl.off_sp = at;
-    at += pg_align((size_t)P * pl.sp_chunks * PG_SP * sizeof(double));
+    at += align256((size_t)P * pl.sp_chunks * PG_SP * sizeof(double));
     pl.off_dn = at;
-    at += pg_align((size_t)N * (N - 1) / 2 * pl.dn_chunks * PG_DN * sizeof(double));
+    at += align256((size_t)N * (N - 1) / 2 * pl.dn_chunks * PG_DN * sizeof(double));
     pl.off_A = at;
-    at += pg_align(n * n * sizeof(double));
+    at += align256(n * n * sizeof(double));
     pl.off_g = at;
-    at += pg_align(n * sizeof(double));
+    at += align256(n * sizeof(double));
     pl.off_totals = at;
-    at += pg_align(4 * sizeof(double));
+    at += align256(4 * sizeof(double));
     pl.bytes = at;
     return pl;
 }

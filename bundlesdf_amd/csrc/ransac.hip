@@ -21,7 +21,7 @@
 //  k_ransac_flags       one block per pair: the rows against the winning pose, the
 //                       flags, their count, min_inliers, and the 17 sums in a fixed
 //                       thread -> row assignment and a fixed order of additions.
-#include "nof_device.h"
+#include "geom_device.h"
 
 #pragma clang fp contract(off)
 
@@ -29,7 +29,6 @@ namespace nof {
 
 constexpr int RANSAC_TILE = 256;      // rows staged per tile = threads of a block: one row per thread
 constexpr int RANSAC_MAX_CHUNKS = 64;
-constexpr int RANSAC_SUMS = 17;
 
 __device__ __forceinline__ uint32_t ransac_hash(uint32_t x) {
     x ^= x >> 16;
@@ -38,16 +37,6 @@ __device__ __forceinline__ uint32_t ransac_hash(uint32_t x) {
     x *= 0x846ca68bu;
     x ^= x >> 16;
     return x;
-}
-
-// The pair's rows [s, s + n), both ends clamped into [0, M] whatever pair_start holds.
-__device__ __forceinline__ void pair_rows(const int32_t *__restrict__ pair_start, int32_t p, int64_t M, int64_t &s,
-                                          int32_t &n) {
-    int64_t a = pair_start[p], b = pair_start[p + 1];
-    a = a < 0 ? 0 : (a > M ? M : a);
-    b = b < a ? a : (b > M ? M : b);
-    s = a;
-    n = (int32_t)(b - a);
 }
 
 // One Jacobi rotation of the symmetric 4x4 A in the (P, Q) plane, accumulated into V (Rutishauser's
@@ -239,15 +228,14 @@ template <> struct alignas(16) RansacRow<true> {
 template <bool NORMALS>
 __device__ __forceinline__ bool ransac_inlier(const double (&T)[12], const RansacRow<NORMALS> &r, double dist_sq,
                                               double cos_normal) {
-    const double dx = r.b[0] - (((T[0] * r.a[0] + T[1] * r.a[1]) + T[2] * r.a[2]) + T[3]);
-    const double dy = r.b[1] - (((T[4] * r.a[0] + T[5] * r.a[1]) + T[6] * r.a[2]) + T[7]);
-    const double dz = r.b[2] - (((T[8] * r.a[0] + T[9] * r.a[1]) + T[10] * r.a[2]) + T[11]);
+    double a[3];
+    xform_point(T, r.a[0], r.a[1], r.a[2], a);
+    const double dx = r.b[0] - a[0], dy = r.b[1] - a[1], dz = r.b[2] - a[2];
     bool in = (dx * dx + dy * dy) + dz * dz <= dist_sq;
     if constexpr (NORMALS) {
-        const double nx = (T[0] * r.na[0] + T[1] * r.na[1]) + T[2] * r.na[2];
-        const double ny = (T[4] * r.na[0] + T[5] * r.na[1]) + T[6] * r.na[2];
-        const double nz = (T[8] * r.na[0] + T[9] * r.na[1]) + T[10] * r.na[2];
-        in = in && (nx * r.nb[0] + ny * r.nb[1]) + nz * r.nb[2] >= cos_normal;
+        double n[3];
+        xform_dir(T, r.na[0], r.na[1], r.na[2], n);
+        in = in && (n[0] * r.nb[0] + n[1] * r.nb[1]) + n[2] * r.nb[2] >= cos_normal;
     }
     return in;
 }
@@ -370,7 +358,7 @@ __global__ __launch_bounds__(256) void k_ransac_flags(const double *__restrict__
                                                       const double *__restrict__ pose_out,
                                                       uint8_t *__restrict__ inlier, int32_t *__restrict__ n_inliers,
                                                       double *__restrict__ sums) {
-    __shared__ double wave_sum[4][RANSAC_SUMS];
+    __shared__ double wave_sum[4][RIGID_SUMS];
     const int32_t p = blockIdx.x;
     int64_t s;
     int32_t n;
@@ -379,9 +367,9 @@ __global__ __launch_bounds__(256) void k_ransac_flags(const double *__restrict__
     double pose[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) pose[k] = pose_out[(size_t)p * 16 + k];
-    double acc[RANSAC_SUMS];
+    double acc[RIGID_SUMS];
 #pragma unroll
-    for (int k = 0; k < RANSAC_SUMS; ++k) acc[k] = 0.0;
+    for (int k = 0; k < RIGID_SUMS; ++k) acc[k] = 0.0;
     for (int32_t r = threadIdx.x; r < n; r += 256) {
         const int64_t i = s + r;
         RansacRow<NORMALS> row;
@@ -389,36 +377,17 @@ __global__ __launch_bounds__(256) void k_ransac_flags(const double *__restrict__
         const bool in = won && ransac_inlier<NORMALS>(pose, row, dist_sq, cos_normal);
         inlier[i] = in ? 1 : 0;
         if (in) {
-            acc[0] += 1.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                acc[1 + a] += row.a[a];
-                acc[4 + a] += row.b[a];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[7 + a * 3 + c] += row.a[a] * row.b[c];
-            }
+            rigid_moments_add(acc, row.a, row.b);
             const double dx = row.b[0] - row.a[0], dy = row.b[1] - row.a[1], dz = row.b[2] - row.a[2];
             acc[16] += (dx * dx + dy * dy) + dz * dz;
         }
     }
-#pragma unroll
-    for (int k = 0; k < RANSAC_SUMS; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < RANSAC_SUMS; ++k) wave_sum[threadIdx.x >> 6][k] = acc[k];
-    }
-    __syncthreads();
+    block_sum_waves<RIGID_SUMS>(acc, wave_sum);
     // the count is a sum of ones below 2^31: exact in f64
-    const double count = ((wave_sum[0][0] + wave_sum[1][0]) + wave_sum[2][0]) + wave_sum[3][0];
+    const double count = wave_total<RIGID_SUMS>(wave_sum, 0);
     const bool clear = count < (double)min_inliers;
-    if (threadIdx.x < RANSAC_SUMS) {
-        const int k = threadIdx.x;
-        sums[(size_t)p * RANSAC_SUMS + k] =
-            clear ? 0.0 : ((wave_sum[0][k] + wave_sum[1][k]) + wave_sum[2][k]) + wave_sum[3][k];
-    }
+    if (threadIdx.x < RIGID_SUMS)
+        sums[(size_t)p * RIGID_SUMS + threadIdx.x] = clear ? 0.0 : wave_total<RIGID_SUMS>(wave_sum, threadIdx.x);
     if (threadIdx.x == 0) n_inliers[p] = clear ? 0 : (int32_t)count;
     if (clear) {
         for (int32_t r = threadIdx.x; r < n; r += 256) inlier[s + r] = 0;     // each thread rewrites its own rows
@@ -446,7 +415,7 @@ size_t nof_ransac_workspace_bytes(int32_t P, int64_t M, int32_t n_trials) {
     (void)M;    // nothing is kept per row
     if (P < 1 || n_trials < 1) return 0;
     const size_t pt = ransac_trials(P, n_trials);
-    return (pt * (12 * sizeof(double) + sizeof(int64_t) + 1) + 255) / 256 * 256;
+    return align256(pt * (12 * sizeof(double) + sizeof(int64_t) + 1));
 }
 
 int nof_ransac_pairs(const nof_ransac_desc *d, void *stream) {

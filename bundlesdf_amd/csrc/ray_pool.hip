@@ -355,8 +355,6 @@ __global__ __launch_bounds__(256) void k_grid_fill(const double *__restrict__ pt
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace nof
 
 using namespace nof;

@@ -5,11 +5,11 @@
 // them into texel coordinates with common.rayColorToTextureImageCUDA and
 // accumulates the first colour per texel with torch.unique + scatter. Here:
 //
-//  k_raster        one thread per face: project (OpenCV pinhole, f64), walk
-//                  the integer pixel centres of the bbox, edge-function
-//                  coverage (either orientation, edges inclusive),
-//                  perspective-correct depth, atomicMin of (depth bits << 32 |
-//                  face) into a 64-bit z-buffer -> depth and face id at once.
+//  k_raster        one thread per face: project_face, then the lane walks the
+//                  integer pixel centres of the box and splats each into the
+//                  64-bit z-buffer -> depth and face id at once. raster.h holds
+//                  the definition of the projection, cull, coverage, depth and
+//                  key, shared with nof_render_mesh.
 //  k_hits          per pixel: depth >= min_depth and the object mask ->
 //                  back-projection (depth2xyzmap arithmetic), camera->object
 //                  transform, closest point on the rasterised face (the
@@ -28,17 +28,15 @@
 //                  the z-buffer inside the screen window that bounds every
 //                  candidate within `radius` (see the kernel), its colour
 //                  added to the vertex's f64 sum and 1 to its count.
-#include <cmath>
-
-#include "nof_device.h"
+#include "raster.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
 
 struct Cam {
-    double R[9], t[3];        // ob -> cam (OpenCV)
-    double fx, fy, cx, cy;
+    double T[12];             // rows of [R | t] (OpenCV)
+    Pinhole k;
 };
 
 __global__ __launch_bounds__(256) void k_raster(const float *__restrict__ V, const int64_t *__restrict__ F,
@@ -46,50 +44,18 @@ __global__ __launch_bounds__(256) void k_raster(const float *__restrict__ V, con
                                                 unsigned long long *__restrict__ zbuf) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= nF) return;
-    double u[3], v[3], z[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float *p = V + F[f * 3 + k] * 3;
-        const double x = p[0], y = p[1], w = p[2];
-        const double X = ((c.R[0] * x + c.R[1] * y) + c.R[2] * w) + c.t[0];
-        const double Y = ((c.R[3] * x + c.R[4] * y) + c.R[5] * w) + c.t[1];
-        const double Z = ((c.R[6] * x + c.R[7] * y) + c.R[8] * w) + c.t[2];
-        if (!(Z > znear)) return;            // no near-plane clipping: faces crossing it are dropped
-        z[k] = Z;
-        u[k] = c.fx * X / Z + c.cx;
-        v[k] = c.fy * Y / Z + c.cy;
-    }
-    const double area = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
-    if (area == 0.0) return;
-    int u0 = (int)ceil(fmin(fmin(u[0], u[1]), u[2])), u1 = (int)floor(fmax(fmax(u[0], u[1]), u[2]));
-    int v0 = (int)ceil(fmin(fmin(v[0], v[1]), v[2])), v1 = (int)floor(fmax(fmax(v[0], v[1]), v[2]));
-    u0 = u0 < 0 ? 0 : u0;
-    v0 = v0 < 0 ? 0 : v0;
-    u1 = u1 > W - 1 ? W - 1 : u1;
-    v1 = v1 > H - 1 ? H - 1 : v1;
-    for (int py = v0; py <= v1; ++py)
-        for (int px = u0; px <= u1; ++px) {
-            const double X = px, Y = py;
-            // barycentric weights of vertex k = edge function of the opposite edge / area
-            const double e0 = ((u[2] - u[1]) * (Y - v[1]) - (v[2] - v[1]) * (X - u[1])) / area;
-            const double e1 = ((u[0] - u[2]) * (Y - v[2]) - (v[0] - v[2]) * (X - u[2])) / area;
-            const double e2 = ((u[1] - u[0]) * (Y - v[0]) - (v[1] - v[0]) * (X - u[0])) / area;
-            if (e0 < 0.0 || e1 < 0.0 || e2 < 0.0) continue;
-            const double zi = 1.0 / ((e0 / z[0] + e1 / z[1]) + e2 / z[2]);
-            if (!(zi <= zfar)) continue;
-            const float zf = (float)zi;
-            const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned long long)f;
-            atomicMin(&zbuf[(size_t)py * W + px], key);
-        }
+    Tri t;
+    if (!project_face(V, F, f, c.T, c.k, H, W, znear, t)) return;
+    for (int py = t.v0; py <= t.v1; ++py)
+        for (int px = t.u0; px <= t.u1; ++px) splat(t, px, py, zfar, (uint32_t)f, W, zbuf);
 }
 
 // Pixel (px, py) of depth z in the object frame: depth2xyzmap (Utils.py:219-231, f64 arithmetic,
 // f32 result) followed by cam_in_ob (`inv`) in f64.
 __device__ __forceinline__ void backproject(const Cam &inv, int px, int py, float z, double p[3]) {
-    const float xc = (float)(((double)px - inv.cx) * (double)z / inv.fx);
-    const float yc = (float)(((double)py - inv.cy) * (double)z / inv.fy);
-    const double pc[3] = {xc, yc, (double)z};
-    for (int k = 0; k < 3; ++k) p[k] = ((inv.R[3 * k] * pc[0] + inv.R[3 * k + 1] * pc[1]) + inv.R[3 * k + 2] * pc[2]) + inv.t[k];
+    const float xc = (float)(((double)px - inv.k.cx) * (double)z / inv.k.fx);
+    const float yc = (float)(((double)py - inv.k.cy) * (double)z / inv.k.fy);
+    xform_point(inv.T, (double)xc, (double)yc, (double)z, p);
 }
 
 // Closest point of triangle (a, b, c) to p (Voronoi-region walk, f64).
@@ -200,15 +166,15 @@ __global__ __launch_bounds__(256) void k_vertex_color(const unsigned long long *
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= nV) return;
     const double vx = V[j * 3], vy = V[j * 3 + 1], vz = V[j * 3 + 2];
-    const double Xv = ((c.R[0] * vx + c.R[1] * vy) + c.R[2] * vz) + c.t[0];
-    const double Yv = ((c.R[3] * vx + c.R[4] * vy) + c.R[5] * vz) + c.t[1];
-    const double Zv = ((c.R[6] * vx + c.R[7] * vy) + c.R[8] * vz) + c.t[2];
+    double Xc[3];
+    xform_point(c.T, vx, vy, vz, Xc);
+    const double Xv = Xc[0], Yv = Xc[1], Zv = Xc[2];
     const double z0 = fmax(Zv - radius, (double)min_depth), z1 = Zv + radius;
     double best = __builtin_inf();
     int best_i = -1;
     int u0, u1, v0, v1;
-    if (z0 <= z1 && pixel_range(c.fx, c.cx, Xv - radius, Xv + radius, z0, z1, W, u0, u1) &&
-        pixel_range(c.fy, c.cy, Yv - radius, Yv + radius, z0, z1, H, v0, v1)) {
+    if (z0 <= z1 && pixel_range(c.k.fx, c.k.cx, Xv - radius, Xv + radius, z0, z1, W, u0, u1) &&
+        pixel_range(c.k.fy, c.k.cy, Yv - radius, Yv + radius, z0, z1, H, v0, v1)) {
         for (int py = v0; py <= v1; ++py)
             for (int px = u0; px <= u1; ++px) {
                 const int i = py * W + px;
@@ -274,11 +240,8 @@ __global__ __launch_bounds__(256) void k_tex_add(const float *__restrict__ uvs, 
 
 static Cam make_cam(const double *T, const double *K) {
     Cam c;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) c.R[3 * r + k] = T[4 * r + k];
-        c.t[r] = T[4 * r + 3];
-    }
-    c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
+    for (int k = 0; k < 12; ++k) c.T[k] = T[k];
+    c.k = {K[0], K[4], K[2], K[5]};
     return c;
 }
 

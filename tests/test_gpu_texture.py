@@ -86,6 +86,51 @@ def test_raster_hits_accumulate_exact(cuda_device):
     assert w_o.sum() > 300
 
 
+def test_raster_far_projecting_faces(cuda_device):
+    """Faces whose projection lies past 2^31 pixels: the bounding box is compared in f64 before it is
+    cast. Face 0 is inside the 8x8 image. Face 1 has a vertex at Z = znear (1 + 1e-12) with X = 1e8
+    (u = 8e9) and its other two left of the image, so its box crosses the image and it covers most of
+    it. Face 2 lies wholly 5e9 pixels to the right. The numpy oracle takes all three (Python integers),
+    and nof_raster_faces, MeshRenderer.render and the oracle must agree key for key."""
+    from bundlesdf_amd import _lib
+    from bundlesdf_amd.mesh import Mesh
+    from bundlesdf_amd.mesh_render import MeshRenderer
+    from oracle import texture as TX
+    H = W = 8
+    znear, zfar = 0.1, 10.0
+    K = np.array([[8.0, 0, 3.5], [0, 8.0, 3.5], [0, 0, 1]])
+    tz = znear * (1 + 1e-12)
+    T = np.eye(4)
+    T[2, 3] = tz        # the vertices are float32: the pose carries the depth just beyond znear
+
+    def at(u, v, w):    # the vertex that projects to pixel (u, v) at depth tz + w
+        return [(u - 3.5) / 8 * (tz + w), (v - 3.5) / 8 * (tz + w), w]
+    verts = np.array([at(1, 1, 0.5), at(6, 2, 0.5), at(2, 6, 0.5),
+                      [1e8, 0.0, 0.0], at(-2, 1, 1.0), at(-2, 7, 1.0),
+                      [1e9, 0.0, 1.0], [1.1e9, 0.0, 1.0], [1e9, 1.0, 1.0]], np.float32)
+    faces = np.arange(9, dtype=np.int64).reshape(3, 3)
+    empty = np.iinfo(np.uint64).max
+    zref = TX.raster(verts, faces, T, K, H, W, znear, zfar)
+    seen = set((zref[zref != empty] & np.uint64(0xffffffff)).tolist())
+    assert seen == {0, 1}                                    # both near faces show, the far one nowhere
+    np.testing.assert_array_equal(zref, TX.raster(verts, faces[:2], T, K, H, W, znear, zfar))
+
+    V = torch.as_tensor(verts, device=cuda_device)
+    F = torch.as_tensor(faces, device=cuda_device)
+    zb = torch.empty(H * W, dtype=torch.int64, device=cuda_device)
+    _lib.check(_lib.lib().nof_raster_faces(_lib.ptr(V), _lib.ptr(F), len(F), T.ctypes.data_as(_lib._p),
+                                           K.ctypes.data_as(_lib._p), H, W, znear, zfar, _lib.ptr(zb),
+                                           _lib.stream_of(V)))
+    np.testing.assert_array_equal(zb.cpu().numpy().view(np.uint64), zref)
+    r = MeshRenderer(Mesh(verts, faces), K, H, W, znear=znear, zfar=zfar, device=cuda_device)
+    for small_max in (0, 1 << 30):                           # every face through k_mesh_large, then none
+        out = r.render(T, colour="flat", small_max_pixels=small_max)
+        depth = out["depth"].cpu().numpy().reshape(-1).view(np.uint32).astype(np.uint64)
+        face = out["face"].cpu().numpy().reshape(-1)
+        keys = np.where(face >= 0, (depth << np.uint64(32)) | face.astype(np.int64).astype(np.uint64), empty)
+        np.testing.assert_array_equal(keys, zref)
+
+
 def test_unwrap_atlas():
     from bundlesdf_amd.texture import unwrap
     mesh = unwrap(_sphere_mesh(), 512)
