@@ -96,6 +96,11 @@ _SIGNATURES = {
     "nof_ransac_pairs": ([_p, _p], _int),
     "nof_pose_graph_workspace_bytes": ([_i32, _i32, _i64, _i32, _i32], ctypes.c_size_t),
     "nof_pose_graph_optimize": ([_p, _p], _int),
+    "nof_frame_erode": ([_p, _p], _int),
+    "nof_frame_bilateral": ([_p, _p], _int),
+    "nof_frame_geometry": ([_p, _p], _int),
+    "nof_frame_lift_matches": ([_p, _p], _int),
+    "nof_frame_covisibility": ([_p, _p], _int),
 }
 
 
@@ -177,6 +182,44 @@ class PoseGraphDesc(ctypes.Structure):
                 ("min_trace", _d), ("workspace", _p), ("workspace_bytes", ctypes.c_size_t), ("poses_out", _p),
                 ("history", _p), ("iter_poses", _p), ("dbg_A", _p), ("dbg_g", _p), ("dbg_delta", _p),
                 ("dense_index", _p)]
+
+
+class FrameErodeDesc(ctypes.Structure):
+    """Mirror of nof_frame_erode_desc (include/nof.h)."""
+    _d = ctypes.c_double
+    _fields_ = [("in_", _p), ("out", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("radius", _i32), ("depth_min", _d),
+                ("zfar", _d), ("diff", _d), ("ratio", _d)]
+
+
+class FrameBilateralDesc(ctypes.Structure):
+    """Mirror of nof_frame_bilateral_desc (include/nof.h)."""
+    _d = ctypes.c_double
+    _fields_ = [("in_", _p), ("out", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("radius", _i32), ("depth_min", _d),
+                ("zfar", _d), ("two_sigma_d_sq", _d), ("two_sigma_r_sq", _d), ("band", _d)]
+
+
+class FrameGeometryDesc(ctypes.Structure):
+    """Mirror of nof_frame_geometry_desc (include/nof.h)."""
+    _d = ctypes.c_double
+    _fields_ = [("depth_in", _p), ("K", _p), ("mask", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("reserved", _i32),
+                ("depth_min", _d), ("z_diff", _d), ("sin_edge", _d), ("depth", _p), ("points", _p), ("normals", _p),
+                ("n_valid", _p)]
+
+
+class FrameLiftDesc(ctypes.Structure):
+    """Mirror of nof_frame_lift_desc (include/nof.h)."""
+    _d = ctypes.c_double
+    _fields_ = [("points", _p), ("normals", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("P", _i32), ("M", _i64),
+                ("pair_frames", _p), ("pair_start", _p), ("uv_a", _p), ("uv_b", _p), ("poses", _p), ("depth_min", _d),
+                ("max_dist", _d), ("cos_normal", _d), ("gate_dist", _i32), ("gate_normal", _i32), ("pts_a", _p),
+                ("pts_b", _p), ("normals_a", _p), ("normals_b", _p), ("valid", _p)]
+
+
+class FrameCovisDesc(ctypes.Structure):
+    """Mirror of nof_frame_covis_desc (include/nof.h)."""
+    _d = ctypes.c_double
+    _fields_ = [("points", _p), ("normals", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("Q", _i32), ("pairs", _p),
+                ("T", _p), ("stride", _i32), ("reserved", _i32), ("depth_min", _d), ("cos_visible", _d), ("counts", _p)]
 
 
 class StepParams(ctypes.Structure):

@@ -942,6 +942,116 @@ size_t nof_pose_graph_workspace_bytes(int32_t N, int32_t P, int64_t M, int32_t H
  * H, W, radius, dist_thresh, a weight below 0, a NaN threshold or intrinsic, workspace_bytes). */
 int nof_pose_graph_optimize(const nof_pose_graph_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 10
+ * Frame maps: from raw depth frames to what groups 8 and 9 start from (the
+ * reference's Frame::processDepth, Frame::depthToCloudAndNormals and
+ * Frame::invalidatePixelsByMask over BundleTrack/src/cuda/CUDAImageUtil.cu, with
+ * SiftManager::makeCorrespondence and computeCovisibility), batched over N frames.
+ *
+ * Depth images are device [N,H,W] f32 in metres, row-major, pixel (u, v) = (column,
+ * row); a non-finite depth is read as 0 everywhere. N is 1 .. 65535, H and W at
+ * least 1, N H W < 2^31. The definition of every call, with the order of every
+ * operation, is the header comment of bundlesdf_amd/csrc/frame_maps.hip: IEEE f64
+ * without contraction from float32 inputs, outputs rounded once to float32,
+ * thresholds taken as the doubles given here, no floating-point atomics, the same
+ * bytes on every run. Every call launches on `stream`, allocates nothing, reads
+ * nothing back, and validates its whole descriptor before the first HIP call:
+ * NOF_EINVAL with nof_last_error naming the field.
+ */
+
+/* e = c unless the centre c fails c > depth_min and c <= zfar, or the share of bad
+ * taps (x < depth_min or |x - c| > diff, taps outside the image not counted) of the
+ * (2 radius + 1)^2 window reaches ratio; then e = 0. in and out are distinct. */
+typedef struct {
+    const float *in;                      /* device [N,H,W] f32 */
+    float *out;                           /* device [N,H,W] f32 */
+    int32_t N, H, W;
+    int32_t radius;                       /* 0 .. 8 */
+    double depth_min, zfar, diff, ratio;
+} nof_frame_erode_desc;
+int nof_frame_erode(const nof_frame_erode_desc *d, void *stream);
+
+/* One pass of the reference's depth-aware Gaussian: the mean of the usable taps
+ * (depth_min <= x <= zfar), then the weighted mean of the usable taps within band of
+ * that mean, w = exp(-(dx^2 + dy^2) / two_sigma_d_sq - (c - x)^2 / two_sigma_r_sq);
+ * 0 where no tap is usable or the weights sum to nothing. An invalid centre is
+ * filled from its neighbours. in and out are distinct. */
+typedef struct {
+    const float *in;                      /* device [N,H,W] f32 */
+    float *out;                           /* device [N,H,W] f32 */
+    int32_t N, H, W;
+    int32_t radius;                       /* 0 .. 8 */
+    double depth_min, zfar;
+    double two_sigma_d_sq, two_sigma_r_sq;  /* 2 sigma^2, formed by the caller, > 0 */
+    double band;
+} nof_frame_bilateral_desc;
+int nof_frame_bilateral(const nof_frame_bilateral_desc *d, void *stream);
+
+/* Camera-space points ((u - cx) z / fx, (v - cy) z / fy, z), normals by the
+ * reference's central / one-sided differences, the grazing-angle filter (a pixel
+ * with a normal is dropped if |n . P/|P|| < sin_edge), the mask, and the count of
+ * the pixels left per frame. depth, points and normals are zero at every dropped
+ * pixel, and every element is written. */
+typedef struct {
+    const float *depth_in;                /* device [N,H,W] f32 */
+    const double *K;                      /* device [N,4] f64: fx, fy, cx, cy of each frame */
+    const uint8_t *mask;                  /* device [N,H,W] u8, 0 drops the pixel; NULL = no mask */
+    int32_t N, H, W;
+    int32_t reserved;
+    double depth_min;
+    double z_diff;                        /* a neighbour takes part in a difference within this of the centre's z */
+    double sin_edge;                      /* sin of the edge angle, formed by the caller */
+    float *depth;                         /* device [N,H,W] f32, not depth_in */
+    float *points, *normals;              /* device [N,H,W,3] f32 */
+    int32_t *n_valid;                     /* device [N] i32, cleared by the call */
+} nof_frame_geometry_desc;
+int nof_frame_geometry(const nof_frame_geometry_desc *d, void *stream);
+
+/* Pixel matches to 3-D matches, in the row layout of group 8: pair p owns rows
+ * pair_start[p] .. pair_start[p+1]-1 and joins frames pair_frames[p] = (a, b). The
+ * coordinates are rounded half away from zero, then bounds-checked; a row is valid
+ * if both pixels exist, both z > depth_min and the optional gates pass (with poses,
+ * camera-in-world: world distance <= max_dist, the unit world normals' dot product
+ * >= cos_normal). Valid rows hold the maps' camera-space entries widened to f64,
+ * invalid rows zeros; rows are not compacted. M == 0 returns 0 without a launch.
+ * The caller makes sure pair_start is monotone from 0 to M. */
+typedef struct {
+    const float *points, *normals;        /* device [N,H,W,3] f32 */
+    int32_t N, H, W;
+    int32_t P;                            /* 1 .. 65535 */
+    int64_t M;                            /* 0 <= M < 2^31 */
+    const int32_t *pair_frames;           /* device [P,2] i32 */
+    const int32_t *pair_start;            /* device [P+1] i32 */
+    const double *uv_a, *uv_b;            /* device [M,2] f64: u (column), v (row) */
+    const double *poses;                  /* device [N,16] f64 or NULL (no gates) */
+    double depth_min;
+    double max_dist;                      /* used with gate_dist */
+    double cos_normal;                    /* used with gate_normal */
+    int32_t gate_dist, gate_normal;       /* 0 = off */
+    double *pts_a, *pts_b;                /* device [M,3] f64 */
+    double *normals_a, *normals_b;        /* device [M,3] f64 */
+    uint8_t *valid;                       /* device [M] u8 */
+} nof_frame_lift_desc;
+int nof_frame_lift_matches(const nof_frame_lift_desc *d, void *stream);
+
+/* For each ordered pair q = (a, b): over every stride-th pixel of frame a from
+ * (0, 0) with z >= depth_min and a non-zero normal, counts[q] = (visible, total),
+ * visible where the unit direction from the moved point to the eye and the moved
+ * unit normal have a dot product above cos_visible. T[q] = inv(pose_b) pose_a,
+ * 4x4 row-major, formed by the caller. Q == 0 returns 0 without a launch. */
+typedef struct {
+    const float *points, *normals;        /* device [N,H,W,3] f32 */
+    int32_t N, H, W;
+    int32_t Q;                            /* 0 .. 65535 */
+    const int32_t *pairs;                 /* device [Q,2] i32 */
+    const double *T;                      /* device [Q,16] f64 */
+    int32_t stride;                       /* >= 1 */
+    int32_t reserved;
+    double depth_min, cos_visible;
+    int32_t *counts;                      /* device [Q,2] i32, cleared by the call */
+} nof_frame_covis_desc;
+int nof_frame_covisibility(const nof_frame_covis_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
