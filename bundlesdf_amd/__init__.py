@@ -10,5 +10,17 @@ reference's operator/module interfaces:
   bundlesdf_amd.grid          <- mycuda/torch_ngp_grid_encoder/grid.py
   bundlesdf_amd.nerf_helpers  <- nerf_helpers.py
   bundlesdf_amd.nerf_runner   <- nerf_runner.py (NerfRunner)
+  bundlesdf_amd.matching      <- BundleTrack/LoFTR/src/loftr/utils/coarse_matching.py (match_descriptors)
 """
 __version__ = "0.1.0"
+
+__all__ = ["matching"]
+
+
+def __getattr__(name):
+    # bundlesdf_amd.matching without an import of its own; loaded on first use so that
+    # `python -m bundlesdf_amd.build` does not pay for torch
+    if name == "matching":
+        import importlib
+        return importlib.import_module(".matching", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

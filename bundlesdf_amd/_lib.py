@@ -101,6 +101,8 @@ _SIGNATURES = {
     "nof_frame_geometry": ([_p, _p], _int),
     "nof_frame_lift_matches": ([_p, _p], _int),
     "nof_frame_covisibility": ([_p, _p], _int),
+    "nof_match_workspace_bytes": ([_i32, _i32, _i32], ctypes.c_size_t),
+    "nof_match_descriptors": ([_p, _p], _int),
 }
 
 
@@ -220,6 +222,15 @@ class FrameCovisDesc(ctypes.Structure):
     _d = ctypes.c_double
     _fields_ = [("points", _p), ("normals", _p), ("N", _i32), ("H", _i32), ("W", _i32), ("Q", _i32), ("pairs", _p),
                 ("T", _p), ("stride", _i32), ("reserved", _i32), ("depth_min", _d), ("cos_visible", _d), ("counts", _p)]
+
+
+class MatchDesc(ctypes.Structure):
+    """Mirror of nof_match_desc (include/nof.h): the descriptors, settings and outputs of nof_match_descriptors."""
+    _fields_ = [("desc_a", _p), ("desc_b", _p), ("valid_a", _p), ("valid_b", _p), ("P", _i32), ("L", _i32), ("S", _i32),
+                ("C", _i32), ("h0", _i32), ("w0", _i32), ("h1", _i32), ("w1", _i32), ("border_rm", _i32),
+                ("reserved", _i32), ("temperature", _f32), ("thr", _f32), ("workspace", _p),
+                ("workspace_bytes", ctypes.c_size_t), ("j_of_i", _p), ("conf", _p), ("n_matches", _p), ("row_max", _p),
+                ("row_sum", _p), ("col_max", _p), ("col_sum", _p)]
 
 
 class StepParams(ctypes.Structure):

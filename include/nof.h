@@ -1052,6 +1052,55 @@ typedef struct {
 } nof_frame_covis_desc;
 int nof_frame_covisibility(const nof_frame_covis_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 11
+ * Descriptor matching: the weight-free matching head of the reference's LoFTR
+ * (BundleTrack/LoFTR/src/loftr/utils/coarse_matching.py: dual-softmax confidence,
+ * threshold, border, mutual nearest neighbours), fused so that no [L,S] array is
+ * ever written: what group 10's lift takes its pixel matches from.
+ *
+ * For P pairs, desc_a [P,L,C] and desc_b [P,S,C] are fp16 descriptors of the cells
+ * of an h0 x w0 and an h1 x w1 grid (row-major, L = h0 w0, S = h1 w1).
+ *   sim(i,j)  = (sum_k a_ik b_jk) * 1/(C temperature): fp16 products accumulated in
+ *               f32 by the MFMA, one f32 scale applied to the sum; -inf where
+ *               valid_a[i] or valid_b[j] is 0.
+ *   conf(i,j) = exp(sim - rowmax_i) / rowsum_i * exp(sim - colmax_j) / colsum_j in
+ *               f32 (row statistics over j, column statistics over i; a division is
+ *               a product with the sum's f32 reciprocal). A row or column with no
+ *               valid partner has max -inf, sum 0 and conf 0 everywhere.
+ *   match     (i,j) iff conf(i,j) > thr, neither cell within border_rm cells of its
+ *               grid's edge, j the lowest index attaining the maximum of row i and i
+ *               the lowest index attaining the maximum of column j.
+ * Every reduction runs in a fixed order and no floating-point atomic is used: the
+ * same bytes on every run. csrc/match.hip's header comment is the full definition. */
+typedef struct {
+    const void *desc_a, *desc_b;          /* device [P,L,C] / [P,S,C] fp16, 16-byte aligned */
+    const uint8_t *valid_a, *valid_b;     /* device [P,L] / [P,S] u8, both or neither */
+    int32_t P;                            /* 1 .. 65535, P L and P S below 2^31 */
+    int32_t L, S;                         /* h0 w0, h1 w1 */
+    int32_t C;                            /* a multiple of 8 in 8 .. 512 */
+    int32_t h0, w0, h1, w1;
+    int32_t border_rm;                    /* >= 0 */
+    int32_t reserved;
+    float temperature;                    /* > 0 */
+    float thr;                            /* in [0, 1) */
+    void *workspace;                      /* device, at least nof_match_workspace_bytes(P, L, S) */
+    size_t workspace_bytes;               /* the size of workspace */
+    int32_t *j_of_i;                      /* device [P,L] i32: the match of row i, -1 for none */
+    float *conf;                          /* device [P,L] f32: its confidence, 0 for none */
+    int32_t *n_matches;                   /* device [P] i32 */
+    /* debug outputs, NULL = kept in the workspace only */
+    float *row_max, *row_sum;             /* device [P,L] f32 */
+    float *col_max, *col_sum;             /* device [P,S] f32 */
+} nof_match_desc;
+
+/* Statistics and best partners per row and column: 7 arrays of P L or P S words, nothing of size L S. */
+size_t nof_match_workspace_bytes(int32_t P, int32_t L, int32_t S);
+
+/* Five launches on `stream` (statistics and best partner, each for rows and columns, then the
+ * emit); nothing is allocated or read back. The whole descriptor is validated before the first HIP
+ * call: NOF_EINVAL with nof_last_error naming the field. */
+int nof_match_descriptors(const nof_match_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
