@@ -103,6 +103,8 @@ _SIGNATURES = {
     "nof_frame_covisibility": ([_p, _p], _int),
     "nof_match_workspace_bytes": ([_i32, _i32, _i32], ctypes.c_size_t),
     "nof_match_descriptors": ([_p, _p], _int),
+    "nof_feature_transformer_workspace_bytes": ([_i32, _i32, _i32, _i32], ctypes.c_size_t),
+    "nof_feature_transformer": ([_p, _p], _int),
 }
 
 
@@ -231,6 +233,18 @@ class MatchDesc(ctypes.Structure):
                 ("reserved", _i32), ("temperature", _f32), ("thr", _f32), ("workspace", _p),
                 ("workspace_bytes", ctypes.c_size_t), ("j_of_i", _p), ("conf", _p), ("n_matches", _p), ("row_max", _p),
                 ("row_sum", _p), ("col_max", _p), ("col_sum", _p)]
+
+
+FT_SELF, FT_CROSS, FT_MAX_LAYERS = 0, 1, 16   # NOF_FT_*
+
+
+class FeatureTransformerDesc(ctypes.Structure):
+    """Mirror of nof_feature_transformer_desc (include/nof.h): the streams, masks, layers and weights of
+    nof_feature_transformer."""
+    _fields_ = [("feat_a", _p), ("feat_b", _p), ("mask_a", _p), ("mask_b", _p), ("P", _i32), ("L", _i32), ("S", _i32),
+                ("C", _i32), ("n_layers", _i32), ("layer_kind", _i32 * FT_MAX_LAYERS), ("reserved", _i32),
+                ("weights", _p), ("weights_bytes", ctypes.c_size_t), ("workspace", _p),
+                ("workspace_bytes", ctypes.c_size_t)]
 
 
 class StepParams(ctypes.Structure):

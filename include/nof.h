@@ -1101,6 +1101,58 @@ size_t nof_match_workspace_bytes(int32_t P, int32_t L, int32_t S);
  * call: NOF_EINVAL with nof_last_error naming the field. */
 int nof_match_descriptors(const nof_match_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 12
+ * Feature transformer: the reference's LocalFeatureTransformer (BundleTrack/LoFTR/
+ * src/loftr/loftr_module/transformer.py, linear_attention.py), the stack of linear-
+ * attention layers between a backbone and group 11's matching head, two fused kernels
+ * and one fixed-order sum per layer application.
+ *
+ * One application x <- layer(x, source), x [L,C], source [S,C], 8 heads of D = C/8:
+ *   Q = elu(x Wq^T) + 1, K = elu(source Wk^T) + 1, V = source Wv^T; Q *= x_mask,
+ *   K *= source_mask, V *= source_mask (a mask byte of 0 takes the row out)
+ *   KV_h = (1/S) sum_s K_h[s]^T V_h[s],  Ksum_h = sum_s K_h[s]
+ *   msg_h[l] = (Q_h[l] KV_h) S / (Q_h[l] . Ksum_h + 1e-6)        S the full length
+ *   m = LayerNorm1(msg Wm^T); m = LayerNorm2(relu([x | m] W1^T) W2^T); out = x + m
+ *   (LayerNorm: eps 1e-5, biased variance, affine; no biases in the linear maps)
+ * NOF_FT_SELF is a <- layer(a, a), b <- layer(b, b); NOF_FT_CROSS is a <- layer(a, b),
+ * then b <- layer(b, a) with the updated a. feat_a and feat_b are float32 and are
+ * updated in place. Every matrix product has fp16 operands and f32 accumulation; elu,
+ * Z, the LayerNorm statistics and the residual add are f32, so a masked row and a
+ * source with no unmasked row give finite values. Every sum runs in a fixed order and
+ * no floating-point atomic is used: the same bytes on every run and for every batching.
+ * csrc/feature_transformer.hip's header comment is the full definition.
+ *
+ * weights: n_layers blocks of 20 C C + 16 C bytes. A block holds Wq, Wk, Wv, Wm [C,C],
+ * W1 [2C,2C] and W2 [C,2C] in fp16, each (out N, in K) matrix in fragment order
+ * [N/32][K/16][64][8] with entry (nt, ks, lane, j) = W[32 nt + lane % 32][16 ks +
+ * 8 (lane / 32) + j], then norm1.weight, norm1.bias, norm2.weight, norm2.bias [C] f32. */
+#define NOF_FT_SELF 0
+#define NOF_FT_CROSS 1
+#define NOF_FT_MAX_LAYERS 16
+typedef struct {
+    float *feat_a, *feat_b;               /* device [P,L,C] / [P,S,C] f32, 16-byte aligned, read and overwritten */
+    const uint8_t *mask_a, *mask_b;       /* device [P,L] / [P,S] u8 or NULL, each on its own */
+    int32_t P;                            /* 1 .. 32767 (2 P problems in one launch) */
+    int32_t L, S;                         /* >= 1 */
+    int32_t C;                            /* 128 or 256 */
+    int32_t n_layers;                     /* 1 .. NOF_FT_MAX_LAYERS */
+    int32_t layer_kind[NOF_FT_MAX_LAYERS];/* NOF_FT_SELF or NOF_FT_CROSS, the first n_layers are read */
+    int32_t reserved;
+    const void *weights;                  /* device, 16-byte aligned, laid out as above */
+    size_t weights_bytes;                 /* at least n_layers (20 C C + 16 C) */
+    void *workspace;                      /* device, 16-byte aligned */
+    size_t workspace_bytes;               /* at least the size the workspace function returns for (P, L, S, C) */
+} nof_feature_transformer_desc;
+
+/* Partial KV and Ksum of every block of 256 source rows, and their sums: 2 P problems; 0 for shapes
+ * that are not supported. */
+size_t nof_feature_transformer_workspace_bytes(int32_t P, int32_t L, int32_t S, int32_t C);
+
+/* Three launches on `stream` per layer application (a self layer applies both sides in one set, a
+ * cross layer takes two); nothing is allocated or read back. The whole descriptor is validated
+ * before the first HIP call: NOF_EINVAL with nof_last_error naming the field. */
+int nof_feature_transformer(const nof_feature_transformer_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
