@@ -105,6 +105,8 @@ _SIGNATURES = {
     "nof_match_descriptors": ([_p, _p], _int),
     "nof_feature_transformer_workspace_bytes": ([_i32, _i32, _i32, _i32], ctypes.c_size_t),
     "nof_feature_transformer": ([_p, _p], _int),
+    "nof_fine_windows": ([_p, _p], _int),
+    "nof_fine_expectation": ([_p, _p], _int),
 }
 
 
@@ -245,6 +247,20 @@ class FeatureTransformerDesc(ctypes.Structure):
                 ("C", _i32), ("n_layers", _i32), ("layer_kind", _i32 * FT_MAX_LAYERS), ("reserved", _i32),
                 ("weights", _p), ("weights_bytes", ctypes.c_size_t), ("workspace", _p),
                 ("workspace_bytes", ctypes.c_size_t)]
+
+
+class FineWindowsDesc(ctypes.Structure):
+    """Mirror of nof_fine_windows_desc (include/nof.h): the maps, matches, weights and outputs of nof_fine_windows."""
+    _fields_ = [("fine_a", _p), ("fine_b", _p), ("coarse_a", _p), ("coarse_b", _p), ("frames_a", _p), ("frames_b", _p),
+                ("pair", _p), ("i", _p), ("j", _p), ("M", _i32), ("P", _i32), ("N_a", _i32), ("N_b", _i32), ("h0", _i32),
+                ("w0", _i32), ("h1", _i32), ("w1", _i32), ("stride", _i32), ("reserved", _i32), ("weights", _p),
+                ("weights_bytes", ctypes.c_size_t), ("context", _p), ("win_a", _p), ("win_b", _p)]
+
+
+class FineExpectationDesc(ctypes.Structure):
+    """Mirror of nof_fine_expectation_desc (include/nof.h)."""
+    _fields_ = [("win_a", _p), ("win_b", _p), ("pair", _p), ("i", _p), ("j", _p), ("M", _i32), ("P", _i32), ("L", _i32),
+                ("S", _i32), ("expec", _p)]
 
 
 class StepParams(ctypes.Structure):

@@ -219,4 +219,40 @@ class FeatureTransformer:
             _lib.check(lib.nof_feature_transformer(ctypes.byref(D), _lib.stream_of(out_a)), what)
         return out_a, out_b
 
+    def forward_inplace(self, a, b):
+        """The stack on a [P,L,C] and b [P,S,C], contiguous float32 tensors on one device, updated where
+        they lie: forward without its copies of the inputs and without masks. Returns (a, b)."""
+        what = "FeatureTransformer.forward_inplace"
+        for t, name in ((a, "a"), (b, "b")):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous float32 [P,n,C] tensor")
+        P, L, C = a.shape
+        S = b.shape[1]
+        if b.shape[0] != P or b.shape[2] != C:
+            raise ValueError(f"{what}: a is {tuple(a.shape)} and b {tuple(b.shape)}: P and C must agree")
+        if C != self.d_model:
+            raise ValueError(f"{what}: C={C} but the weights are for d_model={self.d_model}")
+        if P < 1 or P > MAX_PAIRS:
+            raise ValueError(f"{what}: {P} pairs (1 .. {MAX_PAIRS})")
+        if L < 1 or S < 1:
+            raise ValueError(f"{what}: L={L} and S={S} must be at least 1")
+        if not a.is_cuda or a.device != b.device:
+            raise ValueError(f"{what}: a is on {a.device} and b on {b.device}: one device is needed")
+        lib = _lib.lib()
+        with torch.cuda.device(a.device):
+            w = self._device_weights(a.device)
+            nbytes = int(lib.nof_feature_transformer_workspace_bytes(P, L, S, C))
+            ws = self._workspace.get(w.device)
+            if ws is None or ws.numel() < nbytes:
+                ws = self._workspace[w.device] = torch.empty(max(1, nbytes), dtype=torch.uint8, device=a.device)
+            D = _lib.FeatureTransformerDesc()
+            D.feat_a, D.feat_b = _lib.ptr(a), _lib.ptr(b)
+            D.P, D.L, D.S, D.C, D.n_layers = P, L, S, C, len(self.layer_names)
+            for i, n in enumerate(self.layer_names):
+                D.layer_kind[i] = _KINDS[n]
+            D.weights, D.weights_bytes = _lib.ptr(w), w.numel()
+            D.workspace, D.workspace_bytes = _lib.ptr(ws), ws.numel()
+            _lib.check(lib.nof_feature_transformer(ctypes.byref(D), _lib.stream_of(a)), what)
+        return a, b
+
     __call__ = forward

@@ -1153,6 +1153,66 @@ size_t nof_feature_transformer_workspace_bytes(int32_t P, int32_t L, int32_t S, 
  * before the first HIP call: NOF_EINVAL with nof_last_error naming the field. */
 int nof_feature_transformer(const nof_feature_transformer_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 13
+ * Fine-level match refinement: the reference's FinePreprocess (BundleTrack/LoFTR/src/
+ * loftr/loftr_module/fine_preprocess.py) and FineMatching (utils/fine_matching.py),
+ * the stages before and after its fine transformer, which is group 12 at C = 128
+ * called on win_a / win_b in place between the two entry points.
+ *
+ * Match m has pair p = pair[m], cell i[m] of A's coarse grid h0 x w0 and cell j[m] of
+ * B's h1 x w1; the fine maps are (stride h) x (stride w), channels-last fp16 with 128
+ * channels, and pair p reads map frames_a[p] / frames_b[p] (map p without them).
+ *   fine_window[r] = the fine feature at (stride (cell / w) + ky - 2, stride (cell % w)
+ *                    + kx - 2), r = 5 ky + kx in 0..24, zeros outside the map
+ *   ctx    = Wd coarse[p, cell] + b_down                        Wd [128,256]
+ *   win[r] = Wm[:, :128] fine_window[r] + (Wm[:, 128:] ctx + b_merge)   Wm [128,256]
+ *   sim[r] = win_a[12] . win_b[r] / sqrt(128), heat = softmax_r(sim)
+ *   x = sum heat gx, y = sum heat gy, gx = -1 + kx / 2, gy = -1 + ky / 2
+ *   std = sqrt(max(sum heat gx^2 - x^2, 1e-10)) + sqrt(max(sum heat gy^2 - y^2, 1e-10))
+ * The three matrix products are MFMAs with fp16 operands and f32 accumulation; the
+ * biases and ctx are added in f32; the correlation, the softmax and the moments are
+ * f32. Every sum runs in a fixed order and no floating-point atomic is used: the same
+ * bytes on every run and for every split of the matches into calls. A row whose pair,
+ * cell or frame is out of range is written as zeros and nothing is read for it.
+ * csrc/fine_match.hip's header comment is the full definition.
+ *
+ * weights: Wd [128,256], Wm[:, :128] and Wm[:, 128:] [128,128] in fp16, each in group
+ * 12's fragment order, then b_down and b_merge [128] f32: 132096 bytes. */
+typedef struct {
+    const void *fine_a, *fine_b;          /* device [N_a,stride h0,stride w0,128] / [N_b,stride h1,stride w1,128] fp16 */
+    const float *coarse_a, *coarse_b;     /* device [P,h0 w0,256] / [P,h1 w1,256] f32 */
+    const int32_t *frames_a, *frames_b;   /* device [P] i32 or NULL, each on its own */
+    const int32_t *pair, *i, *j;          /* device [M] i32 */
+    int32_t M;                            /* 0 .. 2^24 */
+    int32_t P;                            /* >= 1 */
+    int32_t N_a, N_b;                     /* >= 1 */
+    int32_t h0, w0, h1, w1;               /* >= 1, stride times each at most 32768 */
+    int32_t stride;                       /* >= 1 */
+    int32_t reserved;
+    const void *weights;                  /* device, laid out as above */
+    size_t weights_bytes;                 /* at least 132096 */
+    float *context;                       /* device [2M,128] f32: ctx of side A's rows, then side B's */
+    float *win_a, *win_b;                 /* device [M,25,128] f32 */
+} nof_fine_windows_desc;
+
+/* Two launches on `stream` (k_fine_context, k_fine_windows); nothing is allocated or read back.
+ * fine_*, coarse_*, weights, context and win_* are 16-byte aligned. The whole descriptor is validated
+ * before the first HIP call: NOF_EINVAL with nof_last_error naming the field. M == 0 returns NOF_OK
+ * with no launch. */
+int nof_fine_windows(const nof_fine_windows_desc *d, void *stream);
+
+typedef struct {
+    const float *win_a, *win_b;           /* device [M,25,128] f32, 16-byte aligned */
+    const int32_t *pair, *i, *j;          /* device [M] i32 */
+    int32_t M;                            /* 0 .. 2^24 */
+    int32_t P;                            /* >= 1 */
+    int32_t L, S;                         /* h0 w0, h1 w1 */
+    float *expec;                         /* device [M,3] f32: x, y, std */
+} nof_fine_expectation_desc;
+
+/* One launch on `stream` (k_fine_expect); validated as above, M == 0 returns NOF_OK with no launch. */
+int nof_fine_expectation(const nof_fine_expectation_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
