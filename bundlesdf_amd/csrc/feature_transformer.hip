@@ -48,22 +48,17 @@
 //              (twice: staged, and again in float32 for the residual), the packed weights and the
 //              output tile.
 //
-// Weights are packed on the host in "fragment order": a matrix W [N,K] (out, in) is stored as
-// [N/32][K/16][64][8] fp16 where entry (nt, ks, lane, j) is W[32 nt + (lane & 31)][16 ks + 8 (lane >> 5)
-// + j], so a wave reads one operand of one MFMA as 1 KB of consecutive bytes. The same fragment is
-// the A operand in k_ft_layer and the B operand in k_ft_kv.
+// Weights are packed on the host in the fragment order of mfma_tile.h, which also defines the lane /
+// register layout of the tiles; the same fragment is the A operand in k_ft_layer and the B operand in
+// k_ft_kv.
 //
 // Tails: a row past L or S is staged as zeros; its K and V are zeroed like a masked row's and its
 // output is not written. There is no scalar path.
-#include "nof_device.h"
+#include "mfma_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
-
-typedef _Float16 fh8v __attribute__((ext_vector_type(8)));
-typedef _Float16 fh4v __attribute__((ext_vector_type(4)));
-typedef float ff16v __attribute__((ext_vector_type(16)));
 
 constexpr int FT_ROWS = 64;                          // tokens of a tile
 constexpr int FT_THREADS = 256;                      // four waves
@@ -82,67 +77,19 @@ struct FtSide {
 struct FtArgs {
     FtSide side[2];            // problem q of a launch is pair q % P of side q / P
     int P;
-    const fh8v *wq, *wk, *wv, *wm, *w1, *w2;   // fragment order
+    const h8v *wq, *wk, *wv, *wm, *w1, *w2;   // fragment order
     const float *ln;           // [4][C]: weight1, bias1, weight2, bias2
     float *part;               // [problems][max_blk][C 32 + C] partial KV and Ksum
-    fh8v *kv;                  // [problems][C/32][2][64] KV / S in fragment order
+    h8v *kv;                   // [problems][C/32][2][64] KV / S in fragment order
     float *ksum;               // [problems][C]
     int max_blk;
 };
-
-// accumulator register 4 g + e of lane half h holds tile row 8 g + 4 h + e
-
-// The 64 staged rows against NT tiles of 32 output channels from tile nt0 of a packed W with KS
-// k-steps. TOKENS_ON_REGS: acc[i][t] has the tokens of half t on the registers and the channels of
-// tile nt0 + i on the lanes; otherwise the channels on the registers and the tokens on the lanes.
-template <int NT, int KS, bool TOKENS_ON_REGS>
-__device__ __forceinline__ void ft_gemm(const fh8v *__restrict__ wp, int nt0, const unsigned char *xs, int row_bytes,
-                                        int lane, ff16v (&acc)[NT][2]) {
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][t][q] = 0.f;
-#pragma unroll 8
-    for (int ks = 0; ks < KS; ++ks) {
-        fh8v w[NT], x[2];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) w[i] = wp[((size_t)(nt0 + i) * KS + ks) * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            x[t] = *reinterpret_cast<const fh8v *>(xs + (32 * t + r) * row_bytes + ks * 32 + h * 16);
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                if constexpr (TOKENS_ON_REGS)
-                    acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[t], w[i], acc[i][t], 0, 0, 0);
-                else
-                    acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[i], x[t], acc[i][t], 0, 0, 0);
-            }
-    }
-}
-
-// rows row0 .. row0 + 63 of base [n,C] float32 as fp16 into dst (rows of row_bytes); zeros past n
-template <int C>
-__device__ __forceinline__ void ft_stage(const float *base, int row0, int n, unsigned char *dst, int row_bytes) {
-    constexpr int Q4 = C / 4;
-    for (int idx = threadIdx.x; idx < FT_ROWS * Q4; idx += FT_THREADS) {
-        const int row = idx / Q4, c4 = idx % Q4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row0 + row < n) v = *reinterpret_cast<const float4 *>(base + (size_t)(row0 + row) * C + c4 * 4);
-        const fh4v o = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        *reinterpret_cast<fh4v *>(dst + row * row_bytes + c4 * 8) = o;
-    }
-}
 
 __device__ __forceinline__ float ft_elu1(float v) { return v > 0.f ? v + 1.0f : expf(v); }
 
 template <int C>
 __global__ void __launch_bounds__(FT_THREADS) k_ft_kv(const FtArgs a) {
-    constexpr int NT = C / 128, KS = C / 16, XROW = 2 * C + 16, TROW = 2 * FT_ROWS + 16;
+    constexpr int NT = C / 128, KS = C / 16, XROW = 2 * C + ROW_PAD, TROW = 2 * FT_ROWS + ROW_PAD;
     __shared__ __attribute__((aligned(16))) unsigned char xs[FT_ROWS * XROW];
     __shared__ __attribute__((aligned(16))) unsigned char kt[C * TROW];
     __shared__ __attribute__((aligned(16))) unsigned char vt[C * TROW];
@@ -157,50 +104,48 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_kv(const FtArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
 
-    ff16v kv[NT];
+    f16v kv[NT];
 #pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) kv[i][e] = 0.f;
+    for (int i = 0; i < NT; ++i) acc_zero(kv[i]);
     float ksum = 0.f;                                // channel threadIdx.x (threads below C)
 
     for (int tile = 0; tile < FT_KV_TILES; ++tile) {
         const int t0 = row0 + tile * FT_ROWS;
         if (t0 >= S) break;
         __syncthreads();                             // the previous tile has been read
-        ft_stage<C>(src, t0, S, xs, XROW);
+        stage_rows<C, FT_ROWS, FT_THREADS>(src, t0, S, xs, XROW);
         if (threadIdx.x < FT_ROWS) {
             const int t = t0 + threadIdx.x;
             keep[threadIdx.x] = (t < S && (mask == nullptr || mask[t] != 0)) ? 1.0f : 0.0f;
         }
         __syncthreads();
 
-        ff16v acc[NT][2];
-        ft_gemm<NT, KS, true>(a.wk, NT * wave, xs, XROW, lane, acc);
+        f16v acc[NT][2];
+        tile_gemm<NT, KS, true>(a.wk, NT * wave, xs, XROW, lane, acc);
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int chan = 32 * (NT * wave + i) + r, tok = 32 * t + 8 * g + 4 * h;
-                    fh4v o;
+                    const int chan = 32 * (NT * wave + i) + r, tok = 32 * t + acc_row(4 * g, h);
+                    h4v o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = (_Float16)(ft_elu1(acc[i][t][4 * g + e]) * keep[tok + e]);
-                    *reinterpret_cast<fh4v *>(kt + chan * TROW + tok * 2) = o;
+                    *reinterpret_cast<h4v *>(kt + chan * TROW + tok * 2) = o;
                 }
-        ft_gemm<NT, KS, true>(a.wv, NT * wave, xs, XROW, lane, acc);
+        tile_gemm<NT, KS, true>(a.wv, NT * wave, xs, XROW, lane, acc);
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int chan = 32 * (NT * wave + i) + r, tok = 32 * t + 8 * g + 4 * h;
-                    fh4v o;
+                    const int chan = 32 * (NT * wave + i) + r, tok = 32 * t + acc_row(4 * g, h);
+                    h4v o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = (_Float16)(acc[i][t][4 * g + e] * keep[tok + e]);
-                    *reinterpret_cast<fh4v *>(vt + chan * TROW + tok * 2) = o;
+                    *reinterpret_cast<h4v *>(vt + chan * TROW + tok * 2) = o;
                 }
         __syncthreads();
 
@@ -209,10 +154,8 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_kv(const FtArgs a) {
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int ks = 0; ks < FT_ROWS / 16; ++ks) {
-                const int off = (32 * (NT * wave + i) + r) * TROW + ks * 32 + h * 16;
-                const fh8v kf = *reinterpret_cast<const fh8v *>(kt + off);
-                const fh8v vf = *reinterpret_cast<const fh8v *>(vt + off);
-                kv[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, vf, kv[i], 0, 0, 0);
+                const int off = (32 * (NT * wave + i) + r) * TROW + ks * 32 + h * 16;   // as lds_operand
+                mma(kv[i], *reinterpret_cast<const h8v *>(kt + off), *reinterpret_cast<const h8v *>(vt + off));
             }
         if (threadIdx.x < C) {
             const _Float16 *row = reinterpret_cast<const _Float16 *>(kt + threadIdx.x * TROW);
@@ -226,10 +169,7 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_kv(const FtArgs a) {
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int d1 = (e & 3) + 8 * (e >> 2) + 4 * h;
-            part[(NT * wave + i) * 1024 + d1 * 32 + r] = kv[i][e];
-        }
+        for (int e = 0; e < 16; ++e) part[(NT * wave + i) * 1024 + acc_row(e, h) * 32 + r] = kv[i][e];
     if (threadIdx.x < C) part[C * 32 + threadIdx.x] = ksum;
 }
 
@@ -259,10 +199,10 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_kvsum(const FtArgs a) {
     }
 }
 
-// LayerNorm over the channels of every token: acc[i][t] holds channels 32 (nt0 + i) + 8 g + 4 h + e
-// (register 4 g + e) of token 32 t + r. Partial sums of the eight (wave, half) pairs meet in red.
+// LayerNorm over the channels of every token: acc[i][t] holds channels 32 (nt0 + i) + acc_row(e, h)
+// (register e) of token 32 t + r. Partial sums of the eight (wave, half) pairs meet in red.
 template <int NT, int C>
-__device__ __forceinline__ void ft_layernorm(ff16v (&acc)[NT][2], float (*red)[8][FT_ROWS], const float *gamma,
+__device__ __forceinline__ void ft_layernorm(f16v (&acc)[NT][2], float (*red)[8][FT_ROWS], const float *gamma,
                                              const float *beta, int nt0, int wave, int lane) {
     const int r = lane & 31, h = lane >> 5;
     float mean[2], rstd[2];
@@ -303,7 +243,7 @@ __device__ __forceinline__ void ft_layernorm(ff16v (&acc)[NT][2], float (*red)[8
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int chan = 32 * (nt0 + i) + 8 * (e >> 2) + 4 * h + (e & 3);
+                const int chan = 32 * (nt0 + i) + acc_row(e, h);
                 acc[i][t][e] = (acc[i][t][e] - mean[t]) * rstd[t] * gamma[chan] + beta[chan];
             }
     }
@@ -311,7 +251,7 @@ __device__ __forceinline__ void ft_layernorm(ff16v (&acc)[NT][2], float (*red)[8
 
 template <int C>
 __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
-    constexpr int NT = C / 128, KS = C / 16, D = C / FT_HEADS, AROW = 4 * C + 16;
+    constexpr int NT = C / 128, KS = C / 16, D = C / FT_HEADS, AROW = 4 * C + ROW_PAD;
     __shared__ __attribute__((aligned(16))) unsigned char buf_a[FT_ROWS * AROW];   // [x | m]
     __shared__ __attribute__((aligned(16))) unsigned char buf_b[FT_ROWS * AROW];   // [Q | msg], then hidden
     __shared__ float red[2][8][FT_ROWS];
@@ -330,7 +270,7 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
     const int r = lane & 31, h = lane >> 5;
     const int nt0 = NT * wave;
 
-    ft_stage<C>(x, row0, L, buf_a, AROW);
+    stage_rows<C, FT_ROWS, FT_THREADS>(x, row0, L, buf_a, AROW);
     for (int i = threadIdx.x; i < C; i += FT_THREADS) ksum[i] = a.ksum[(size_t)q * C + i];
     for (int i = threadIdx.x; i < 4 * C; i += FT_THREADS) lnp[i] = a.ln[i];
     if (threadIdx.x < FT_ROWS) {
@@ -339,12 +279,12 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
     }
     __syncthreads();
 
-    ff16v acc[NT][2];
-    // every epilogue: 4 consecutive channels of one token, 8 bytes into an LDS row
-    auto chan_of = [&](int nt, int g) { return 32 * nt + 8 * g + 4 * h; };
+    f16v acc[NT][2];
+    // every epilogue: 4 consecutive channels of one token (registers 4 g .. 4 g + 3), 8 bytes into an LDS row
+    auto chan_of = [&](int nt, int g) { return 32 * nt + acc_row(4 * g, h); };
 
     // Q = (elu(x Wq^T) + 1) x_mask -> buf_b[:, 0:C]
-    ft_gemm<NT, KS, false>(a.wq, nt0, buf_a, AROW, lane, acc);
+    tile_gemm<NT, KS, false>(a.wq, nt0, buf_a, AROW, lane, acc);
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -352,10 +292,8 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int tok = 32 * t + r;
-                fh4v o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (_Float16)(ft_elu1(acc[i][t][4 * g + e]) * keep[tok]);
-                *reinterpret_cast<fh4v *>(buf_b + tok * AROW + chan_of(nt0 + i, g) * 2) = o;
+                *reinterpret_cast<h4v *>(buf_b + tok * AROW + chan_of(nt0 + i, g) * 2) =
+                    acc_quad(acc[i][t], g, [&](float v, int) { return ft_elu1(v) * keep[tok]; });
             }
     __syncthreads();
 
@@ -372,20 +310,16 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
 
     // msg = (Q KV / S) factor -> buf_b[:, C:2C]: tile nt of msg needs the 32 channels nt of Q only
     {
-        const fh8v *kv = a.kv + (size_t)q * (C / 32) * 2 * 64;
+        const h8v *kv = a.kv + (size_t)q * (C / 32) * 2 * 64;
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
+                acc_zero(acc[i][t]);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][t][e] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const fh8v kf = kv[((nt0 + i) * 2 + ks) * 64 + lane];
-                    const fh8v qf = *reinterpret_cast<const fh8v *>(buf_b + (32 * t + r) * AROW + (nt0 + i) * 64 +
-                                                                    ks * 32 + h * 16);
-                    acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, acc[i][t], 0, 0, 0);
-                }
+                for (int ks = 0; ks < 2; ++ks)
+                    mma(acc[i][t], packed_operand(kv, nt0 + i, 2, ks, lane),
+                        lds_operand(buf_b + (nt0 + i) * 64, 32 * t + r, AROW, ks, h));
             }
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -395,53 +329,45 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
                 for (int g = 0; g < 4; ++g) {
                     const int tok = 32 * t + r, chan = chan_of(nt0 + i, g);
                     const float f = zf[tok][chan / D];           // 4 consecutive channels share a head
-                    fh4v o;
+                    h4v o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = (_Float16)(acc[i][t][4 * g + e] * f);
-                    *reinterpret_cast<fh4v *>(buf_b + tok * AROW + (C + chan) * 2) = o;
+                    *reinterpret_cast<h4v *>(buf_b + tok * AROW + (C + chan) * 2) = o;
                 }
     }
     __syncthreads();
 
     // m = LayerNorm1(msg Wm^T) -> buf_a[:, C:2C]
-    ft_gemm<NT, KS, false>(a.wm, nt0, buf_b + 2 * C, AROW, lane, acc);
+    tile_gemm<NT, KS, false>(a.wm, nt0, buf_b + 2 * C, AROW, lane, acc);
     ft_layernorm<NT, C>(acc, red, lnp, lnp + C, nt0, wave, lane);
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int tok = 32 * t + r;
-                fh4v o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[i][t][4 * g + e];
-                *reinterpret_cast<fh4v *>(buf_a + tok * AROW + (C + chan_of(nt0 + i, g)) * 2) = o;
-            }
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<h4v *>(buf_a + (32 * t + r) * AROW + (C + chan_of(nt0 + i, g)) * 2) =
+                    acc_quad(acc[i][t], g, [](float v, int) { return v; });
     __syncthreads();
 
     // hidden = relu([x | m] W1^T) -> buf_b[:, 0:2C], two chunks of C channels
 #pragma unroll 1
     for (int c = 0; c < 2; ++c) {
         const int n0 = (c * 4 + wave) * NT;
-        ft_gemm<NT, 2 * KS, false>(a.w1, n0, buf_a, AROW, lane, acc);
+        tile_gemm<NT, 2 * KS, false>(a.w1, n0, buf_a, AROW, lane, acc);
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int tok = 32 * t + r;
-                    fh4v o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (_Float16)fmaxf(acc[i][t][4 * g + e], 0.f);
-                    *reinterpret_cast<fh4v *>(buf_b + tok * AROW + chan_of(n0 + i, g) * 2) = o;
-                }
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<h4v *>(buf_b + (32 * t + r) * AROW + chan_of(n0 + i, g) * 2) =
+                        acc_quad(acc[i][t], g, [](float v, int) { return fmaxf(v, 0.f); });
     }
     __syncthreads();
 
     // out = x + LayerNorm2(hidden W2^T)
-    ft_gemm<NT, 2 * KS, false>(a.w2, nt0, buf_b, AROW, lane, acc);
+    tile_gemm<NT, 2 * KS, false>(a.w2, nt0, buf_b, AROW, lane, acc);
     ft_layernorm<NT, C>(acc, red, lnp + 2 * C, lnp + 3 * C, nt0, wave, lane);
 #pragma unroll
     for (int i = 0; i < NT; ++i)
@@ -465,7 +391,7 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
 
 struct FtWs {
     float *part;
-    fh8v *kv;
+    h8v *kv;
     float *ksum;
     int max_blk;
 };
@@ -478,7 +404,7 @@ static size_t ft_carve(void *base, int32_t P, int32_t L, int32_t S, int32_t C, F
     char *b = static_cast<char *>(base);
     if (ws) {
         ws->part = (float *)b;
-        ws->kv = (fh8v *)(b + n_part);
+        ws->kv = (h8v *)(b + n_part);
         ws->ksum = (float *)(b + n_part + n_kv);
         ws->max_blk = max_blk;
     }
@@ -546,8 +472,8 @@ int nof_feature_transformer(const nof_feature_transformer_desc *d, void *stream)
         const size_t cc = (size_t)C * C * 2;
         FtArgs a{};
         a.P = d->P;
-        a.wq = (const fh8v *)w; a.wk = (const fh8v *)(w + cc); a.wv = (const fh8v *)(w + 2 * cc);
-        a.wm = (const fh8v *)(w + 3 * cc); a.w1 = (const fh8v *)(w + 4 * cc); a.w2 = (const fh8v *)(w + 8 * cc);
+        a.wq = (const h8v *)w; a.wk = (const h8v *)(w + cc); a.wv = (const h8v *)(w + 2 * cc);
+        a.wm = (const h8v *)(w + 3 * cc); a.w1 = (const h8v *)(w + 4 * cc); a.w2 = (const h8v *)(w + 8 * cc);
         a.ln = (const float *)(w + 10 * cc);
         a.part = ws.part; a.kv = ws.kv; a.ksum = ws.ksum; a.max_blk = ws.max_blk;
         auto apply = [&](int problems, int max_x, int max_src) {

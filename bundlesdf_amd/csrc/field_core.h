@@ -1,10 +1,10 @@
 // The device core the training step (field_step.hip) and the inference side (field_infer.hip) share:
-// FieldArgs, the MFMA fragment and wave helpers, the sampler, the forward encode, the MLP forward, the
+// FieldArgs, the MFMA fragment (on mfma_tile.h) and wave helpers, the sampler, the forward encode, the MLP forward, the
 // ray context, the SH input, the LDS staging of weight fragments. Device functions only, no kernel.
 #pragma once
 #include <type_traits>
 
-#include "nof_device.h"
+#include "mfma_tile.h"
 #include "ray_trace.h"
 #include "mlp_lds.h"
 
@@ -21,9 +21,6 @@
 #define ABL_SKIPQ(q) ((q) < 2 ? (1 << (23 + (q))) : (1 << (27 + (q))))
 
 namespace nof {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 constexpr int MLP_N_MAX = 9107 + 64 * 3;   // NeRFSmall(2x64, geo 15, colour 3x64), input <= 32, views 9 (+ <= 3 frame features)
 // flat-parameter offsets (MLP_KEYS order, bundlesdf_amd/mlp_layout.py) for input width IN
@@ -129,8 +126,6 @@ __device__ __forceinline__ const FieldArgs &late_args() {
 }
 
 // ----------------------------------------------------------------- helpers
-__device__ __forceinline__ int acc_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
-
 // Wave reductions on DPP (no LDS traffic): inclusive prefix sums inside each 16-lane
 // row (row_shr 1, 2, 4, 8), then row_bcast:15 carries row totals into rows 1 / 3 and
 // row_bcast:31 the first half's total into the second half. Must be called with the
@@ -204,9 +199,7 @@ template <typename TM> __device__ __forceinline__ void frag_zero(typename FragT<
     for (int j = 0; j < 8; ++j) frag_set<TM>(f, j, 0.f);
 }
 
-__device__ __forceinline__ void mma(f16v &acc, const h8v &a, const h8v &b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-}
+// the float32 path of mma (fp16: mfma_tile.h)
 __device__ __forceinline__ void mma(f16v &acc, const FragT<float>::T &a, const FragT<float>::T &b) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[j], b.v[j], acc, 0, 0, 0);
@@ -231,10 +224,6 @@ __device__ __forceinline__ typename FragT<TM>::T load_frag(const void *frags, in
 __device__ __forceinline__ void acc_init_bias(f16v &acc, const float *bias_row64, int mt, int h) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = bias_row64[32 * mt + acc_row(q, h)];
-}
-__device__ __forceinline__ void acc_zero(f16v &acc) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
 }
 // fp16 pair helpers (packed instructions: one v_cvt_pk_f16_f32 / v_pk_max_f16 /
 // v_and_b32 per two elements instead of per-element convert / max / select)

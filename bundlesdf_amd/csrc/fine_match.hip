@@ -39,22 +39,18 @@
 //  k_fine_windows  a wave takes one window as a 32-row tile with 25 live rows: lane (r, half) reads row
 //                  r's 8 fp16 of every k-step straight from the fine map as the MFMA's B operand, so
 //                  nothing goes through LDS. Wm[:, :128] stays in registers (32 fragments per lane, in
-//                  the fragment order of group 12) while the block loops over windows. Adds ctx and
+//                  the fragment order of mfma_tile.h) while the block loops over windows. Adds ctx and
 //                  writes float32 [M,25,128] per side: what nof_feature_transformer updates in place.
 //  k_fine_expect   a wave per match: 25 dot products, the softmax and the moments.
 //
 // Indices come from device memory: every kernel checks pair against P and the cells against their grids
 // (k_fine_windows also the frame against N) before it forms an address. A row that fails is written as
 // zeros (context, window and expec alike) and nothing is read for it.
-#include "nof_device.h"
+#include "mfma_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
-
-typedef _Float16 fh8v __attribute__((ext_vector_type(8)));
-typedef _Float16 fh4v __attribute__((ext_vector_type(4)));
-typedef float ff16v __attribute__((ext_vector_type(16)));
 
 constexpr int FM_C = 128;                            // fine channels
 constexpr int FM_CC = 256;                           // coarse channels
@@ -72,7 +68,7 @@ struct FmArgs {
     int M, P;
     int N[2], h[2], w[2];
     int stride;
-    const fh8v *w_down, *w_fine, *w_ctx;   // fragment order
+    const h8v *w_down, *w_fine, *w_ctx;    // fragment order (mfma_tile.h)
     const float *b_down, *b_merge;
     float *ctx;                // [2M,128]
     float *win[2];             // [M,25,128]
@@ -86,7 +82,7 @@ __device__ __forceinline__ bool fm_row(const int32_t *pair, const int32_t *cell,
 }
 
 __global__ void __launch_bounds__(FM_THREADS) k_fine_context(const FmArgs a) {
-    constexpr int XROW = 2 * FM_CC + 16, YROW = 2 * FM_C + 16;
+    constexpr int XROW = 2 * FM_CC + ROW_PAD, YROW = 2 * FM_C + ROW_PAD;
     __shared__ __attribute__((aligned(16))) unsigned char xs[FM_CTX_ROWS * XROW];   // coarse rows, fp16
     __shared__ __attribute__((aligned(16))) unsigned char ys[FM_CTX_ROWS * YROW];   // Wd coarse + b_down, fp16
     __shared__ int ok[FM_CTX_ROWS];
@@ -109,40 +105,32 @@ __global__ void __launch_bounds__(FM_THREADS) k_fine_context(const FmArgs a) {
             const int c4 = part * 8 + k;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (src) v = *reinterpret_cast<const float4 *>(src + c4 * 4);
-            const fh4v o = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-            *reinterpret_cast<fh4v *>(xs + row * XROW + c4 * 8) = o;
+            const h4v o = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+            *reinterpret_cast<h4v *>(xs + row * XROW + c4 * 8) = o;
         }
     }
     __syncthreads();
 
-    // accumulator register 4 g + e of lane (r, h) holds channel 32 wave + 8 g + 4 h + e of row r
-    ff16v acc;
+    // channels 32 wave + acc_row(., h) on the registers (8 g + 4 h = acc_row(4 g, h)), the tile's rows on the lanes
+    f16v acc;
+    acc_zero(acc);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < FM_CC / 16; ++ks) {
-        const fh8v wf = a.w_down[(wave * (FM_CC / 16) + ks) * 64 + lane];
-        const fh8v xf = *reinterpret_cast<const fh8v *>(xs + r * XROW + ks * 32 + h * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, xf, acc, 0, 0, 0);
-    }
+    for (int ks = 0; ks < FM_CC / 16; ++ks)
+        mma(acc, packed_operand(a.w_down, wave, FM_CC / 16, ks, lane), lds_operand(xs, r, XROW, ks, h));
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int chan = 32 * wave + 8 * g + 4 * h;
         const float4 b = *reinterpret_cast<const float4 *>(a.b_down + chan);
-        const fh4v o = {(_Float16)(acc[4 * g + 0] + b.x), (_Float16)(acc[4 * g + 1] + b.y),
-                        (_Float16)(acc[4 * g + 2] + b.z), (_Float16)(acc[4 * g + 3] + b.w)};
-        *reinterpret_cast<fh4v *>(ys + r * YROW + chan * 2) = o;
+        const h4v o = {(_Float16)(acc[4 * g + 0] + b.x), (_Float16)(acc[4 * g + 1] + b.y),
+                       (_Float16)(acc[4 * g + 2] + b.z), (_Float16)(acc[4 * g + 3] + b.w)};
+        *reinterpret_cast<h4v *>(ys + r * YROW + chan * 2) = o;
     }
     __syncthreads();
 
+    acc_zero(acc);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < FM_C / 16; ++ks) {
-        const fh8v wf = a.w_ctx[(wave * (FM_C / 16) + ks) * 64 + lane];
-        const fh8v xf = *reinterpret_cast<const fh8v *>(ys + r * YROW + ks * 32 + h * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, xf, acc, 0, 0, 0);
-    }
+    for (int ks = 0; ks < FM_C / 16; ++ks)
+        mma(acc, packed_operand(a.w_ctx, wave, FM_C / 16, ks, lane), lds_operand(ys, r, YROW, ks, h));
     const int q = q0 + r;
     if (q < rows) {
         const bool live = ok[r] != 0;
@@ -163,11 +151,11 @@ __global__ void __launch_bounds__(FM_THREADS, 2) k_fine_windows(const FmArgs a) 
     const int r = lane & 31, h = lane >> 5;
     const int ky = r / 5, kx = r - 5 * ky;           // rows 25 .. 31 of the tile are not live
 
-    fh8v wm[NT][KS];                                 // Wm[:, :128], once per block
+    h8v wm[NT][KS];                                  // Wm[:, :128], once per block
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) wm[nt][ks] = a.w_fine[(nt * KS + ks) * 64 + lane];
+        for (int ks = 0; ks < KS; ++ks) wm[nt][ks] = packed_operand(a.w_fine, nt, KS, ks, lane);
 
     const int rows = 2 * a.M;
     for (int q = blockIdx.x * 4 + wave; q < rows; q += gridDim.x * 4) {
@@ -190,36 +178,33 @@ __global__ void __launch_bounds__(FM_THREADS, 2) k_fine_windows(const FmArgs a) 
         const int y = a.stride * cy + ky - 2, x = a.stride * cx + kx - 2;
         const bool live = r < FM_WW && y >= 0 && y < hf && x >= 0 && x < wf;
 
-        fh8v xf[KS];
+        h8v xf[KS];
         if (live) {
             const _Float16 *px = a.fine[sd] + (((size_t)f * hf + y) * wf + x) * FM_C + 8 * h;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) xf[ks] = *reinterpret_cast<const fh8v *>(px + 16 * ks);
+            for (int ks = 0; ks < KS; ++ks) xf[ks] = *reinterpret_cast<const h8v *>(px + 16 * ks);
         } else {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) xf[ks][e] = (_Float16)0.f;
         }
-        ff16v acc[NT];
+        f16v acc[NT];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[nt][e] = 0.f;
+        for (int nt = 0; nt < NT; ++nt) acc_zero(acc[nt]);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wm[nt][ks], xf[ks], acc[nt], 0, 0, 0);
+            for (int nt = 0; nt < NT; ++nt) mma(acc[nt], wm[nt][ks], xf[ks]);
 
-        // register 4 g + e of lane (r, h) holds channel 32 nt + 8 g + 4 h + e of window row r
+        // channels 32 nt + acc_row(., h) on the registers, window row r on the lanes
         if (r < FM_WW) {
             const float *ctx = a.ctx + (size_t)q * FM_C;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int chan = 32 * nt + 8 * g + 4 * h;
+                    const int chan = 32 * nt + acc_row(4 * g, h);
                     const float4 cv = *reinterpret_cast<const float4 *>(ctx + chan);
                     const float4 v = make_float4(acc[nt][4 * g + 0] + cv.x, acc[nt][4 * g + 1] + cv.y,
                                                  acc[nt][4 * g + 2] + cv.z, acc[nt][4 * g + 3] + cv.w);
@@ -342,9 +327,9 @@ int nof_fine_windows(const nof_fine_windows_desc *d, void *stream) {
     a.N[0] = d->N_a; a.N[1] = d->N_b;
     a.h[0] = d->h0; a.w[0] = d->w0; a.h[1] = d->h1; a.w[1] = d->w1;
     a.stride = d->stride;
-    a.w_down = (const fh8v *)w;
-    a.w_fine = (const fh8v *)(w + (size_t)FM_C * FM_CC * 2);
-    a.w_ctx = (const fh8v *)(w + (size_t)FM_C * FM_CC * 2 + (size_t)FM_C * FM_C * 2);
+    a.w_down = (const h8v *)w;
+    a.w_fine = (const h8v *)(w + (size_t)FM_C * FM_CC * 2);
+    a.w_ctx = (const h8v *)(w + (size_t)FM_C * FM_CC * 2 + (size_t)FM_C * FM_C * 2);
     a.b_down = (const float *)(w + (size_t)2 * FM_C * FM_CC * 2);
     a.b_merge = a.b_down + FM_C;
     a.ctx = d->context; a.win[0] = d->win_a; a.win[1] = d->win_b;

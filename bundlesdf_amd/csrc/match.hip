@@ -25,7 +25,7 @@
 //
 //  k_match_stats  "queries" on the lanes, "keys" in the accumulator registers: a wave owns 32
 //                 queries whose descriptor fragments stay in registers, a block of four waves stages
-//                 tiles of 32 keys in LDS (rows padded by 16 bytes against bank conflicts) and every
+//                 tiles of 32 keys in LDS (rows padded, mfma_tile.h) and every
 //                 wave multiplies the tile against its queries, C/16 MFMAs of 32x32x16 per tile. A
 //                 lane then holds sim of ONE query against 16 keys and keeps that query's running
 //                 maximum and running sum of exp(sim - max) without any cross-lane step; the two
@@ -38,14 +38,11 @@
 // Tails: a query or key row past L or S is staged as zeros and masked to -inf, a k-chunk past C is
 // staged as zeros (C is a multiple of 8, the chunk of one lane); there is no scalar path. No
 // floating-point atomics, no reduction whose order depends on scheduling.
-#include "nof_device.h"
+#include "mfma_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace nof {
-
-typedef _Float16 mh8v __attribute__((ext_vector_type(8)));
-typedef float mf16v __attribute__((ext_vector_type(16)));
 
 constexpr int MATCH_WAVES = 4;                       // waves of a block: 128 queries
 constexpr int MATCH_QB = 32 * MATCH_WAVES;
@@ -65,13 +62,10 @@ struct MatchSide {
     float *best_conf;        // [P,nq] or null
 };
 
-// accumulator register q of lane half h holds tile row (q & 3) + 8 (q >> 2) + 4 h
-__device__ __forceinline__ int match_acc_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
-
 // KS = 16-wide k-steps held (C <= 16 KS). BEST = false: statistics; true: best partner.
 template <int KS, bool BEST>
 __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSide a) {
-    constexpr int ROW_BYTES = KS * 32 + 16;          // a staged key row: 16 KS halves plus the pad
+    constexpr int ROW_BYTES = KS * 32 + ROW_PAD;     // a staged key row: 16 KS halves plus the pad
     constexpr int CHUNKS = KS * 2;                   // 16-byte chunks of a row
     __shared__ __attribute__((aligned(16))) unsigned char tile[MATCH_KT * ROW_BYTES];
     __shared__ float key_max[MATCH_KT], key_rinv[MATCH_KT];
@@ -86,12 +80,12 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSid
     const bool q_ok = q_in && (a.valid_q == nullptr || a.valid_q[qrow] != 0);
 
     // the queries' fragments: lane (r, h) holds Q[query r][16 s + 8 h .. + 7] for every k-step s
-    mh8v qf[KS];
+    h8v qf[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         const int k0 = 16 * s + 8 * h;
-        mh8v v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q_in && k0 < a.C) v = *reinterpret_cast<const mh8v *>(a.q + qrow * a.C + k0);
+        h8v v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (q_in && k0 < a.C) v = *reinterpret_cast<const h8v *>(a.q + qrow * a.C + k0);
         qf[s] = v;
     }
 
@@ -111,10 +105,10 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSid
         __syncthreads();                             // the previous tile has been read by every wave
         for (int idx = threadIdx.x; idx < MATCH_KT * CHUNKS; idx += 64 * MATCH_WAVES) {
             const int row = idx / CHUNKS, ch = idx % CHUNKS;
-            mh8v v = {0, 0, 0, 0, 0, 0, 0, 0};
+            h8v v = {0, 0, 0, 0, 0, 0, 0, 0};
             if (key0 + row < a.nk && ch * 8 < a.C)
-                v = *reinterpret_cast<const mh8v *>(a.k + ((size_t)p * a.nk + key0 + row) * a.C + ch * 8);
-            *reinterpret_cast<mh8v *>(tile + row * ROW_BYTES + ch * 16) = v;
+                v = *reinterpret_cast<const h8v *>(a.k + ((size_t)p * a.nk + key0 + row) * a.C + ch * 8);
+            *reinterpret_cast<h8v *>(tile + row * ROW_BYTES + ch * 16) = v;
         }
         if (threadIdx.x < MATCH_KT) {
             const int key = key0 + threadIdx.x;
@@ -131,15 +125,13 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSid
         }
         __syncthreads();
 
-        mf16v acc;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+        f16v acc;
+        acc_zero(acc);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             // A operand: lane (r, h) holds K[key r][16 s + 8 h .. + 7]; the result has the key on the
             // register axis and the query on the lane
-            const mh8v kf = *reinterpret_cast<const mh8v *>(tile + r * ROW_BYTES + s * 32 + h * 16);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], acc, 0, 0, 0);
+            mma(acc, lds_operand(tile, r, ROW_BYTES, s, h), qf[s]);
         }
 
         if (!BEST) {
@@ -147,7 +139,7 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSid
             float tmax = -INFINITY;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const bool ok = q_ok && key_ok[match_acc_row(q, h)] != 0;
+                const bool ok = q_ok && key_ok[acc_row(q, h)] != 0;
                 v[q] = ok ? acc[q] * a.scale : -INFINITY;
                 tmax = fmaxf(tmax, v[q]);
             }
@@ -162,7 +154,7 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) k_match_tiles(const MatchSid
         } else {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int row = match_acc_row(q, h);
+                const int row = acc_row(q, h);
                 if (key0 + row < a.nk) {
                     const float v = acc[q] * a.scale;
                     const float kr = key_rinv[row];

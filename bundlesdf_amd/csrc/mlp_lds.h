@@ -2,7 +2,7 @@
 //
 // A 32x32x16 f16 MFMA operand fragment in the "normal" layout of the MLP chain holds, in lane
 // n + 32 h (n = sample of the tile), element j of K step s = unit 16 s + 8 (j >> 2) + 4 h +
-// (j & 3) of a 32-unit block (the accumulator row order, field_core.h acc_row). The weight
+// (j & 3) of a 32-unit block (the accumulator row order, mfma_tile.h acc_row). The weight
 // gradients need the same values with the samples as K: lane = unit, element j = sample
 // 16 ks + 8 h + j. Instead of recomputing every activation / gradient a second time with the
 // MFMA operands swapped (and converting it again), the normal fragment is written once into
@@ -16,14 +16,11 @@
 // rows r0 .. r0 + 3 x both 16-unit groups, i.e. 4 rows x 8 slots = all 64 banks, whatever the
 // XOR. The read needs the whole wave active (EXEC all ones: the gather crosses lanes).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mfma_tile.h"
 
 namespace nof {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 constexpr int IMG_BYTES = 32 * 64;   // one [32 samples][32 units] fp16 block
 

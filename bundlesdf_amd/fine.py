@@ -96,7 +96,7 @@ class FineRefiner:
 
     weights maps the reference's parameter names (fine_preprocess.down_proj.{weight,bias} [128,256],
     fine_preprocess.merge_feat.{weight,bias} [128,256], loftr_fine.layers.{i}...) to arrays or tensors.
-    The two matrices are rounded once to float16 and put in FeatureTransformer's fragment order
+    The two matrices are rounded once to float16 and put in the fragment order of csrc/mfma_tile.h
     (merge_feat as its fine half and its context half), the biases stay float32: one buffer (.packed,
     uint8). .transformer is the FeatureTransformer of loftr_fine."""
 

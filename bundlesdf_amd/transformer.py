@@ -68,8 +68,7 @@ def add_position_encoding(feat, temp_bug_fix=False):
 
 
 def pack_matrix(W):
-    """W [N,K] float16 (out, in) -> the fragment order of include/nof.h group 12, [N/32][K/16][64][8]:
-    entry (nt, ks, lane, j) is W[32 nt + lane % 32][16 ks + 8 (lane // 32) + j]."""
+    """W [N,K] float16 (out, in) -> the fragment order csrc/mfma_tile.h defines, [N/32][K/16][64][8]."""
     N, K = W.shape
     return np.ascontiguousarray(W.reshape(N // 32, 32, K // 16, 2, 8).transpose(0, 2, 3, 1, 4))
 
