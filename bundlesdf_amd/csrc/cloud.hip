@@ -17,6 +17,7 @@
 //                    sklearn starts it); border -> root of its lowest-index
 //                    core neighbour; noise -> -1.
 #include "geom_device.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -129,6 +130,21 @@ __global__ __launch_bounds__(256) void k_label(PointGrid g, const double *__rest
     labels[i] = best == 0x7fffffff ? -1 : parent[best];
 }
 
+struct DbscanWs : Carver {
+    int32_t *start, *ids, *parent, *changed;
+    double *cpts;
+    uint8_t *core;
+    void *grid;      // the point grid's own workspace
+    DbscanWs(void *base, int32_t n, int64_t n_cells) : Carver(base) {
+        start = take<int32_t>((size_t)(n_cells + 1));
+        cpts = take<double>((size_t)n * 3);
+        ids = take<int32_t>((size_t)n); parent = take<int32_t>((size_t)n);
+        core = take<uint8_t>((size_t)n);
+        changed = take<int32_t>(1);         // the convergence flag, alone in its 256 bytes
+        grid = take<char>(nof_point_grid_workspace_bytes(n_cells));
+    }
+};
+
 }  // namespace nof
 
 using namespace nof;
@@ -145,8 +161,7 @@ int nof_knn_mean_dist(const double *points, int32_t n, int32_t k, double *mean_d
 }
 
 size_t nof_dbscan_workspace_bytes(int32_t n, int64_t n_cells) {
-    return align256((size_t)(n_cells + 1) * 4) + align256((size_t)n * 24) + align256((size_t)n * 4) * 2 +
-           align256((size_t)n) + 256 + nof_point_grid_workspace_bytes(n_cells);
+    return DbscanWs(nullptr, n, n_cells).bytes;
 }
 
 int nof_dbscan(const double *points, int32_t n, double eps, int32_t min_samples, const double *origin,
@@ -158,35 +173,23 @@ int nof_dbscan(const double *points, int32_t n, double eps, int32_t min_samples,
     if (nc > (1ll << 26)) return set_error(NOF_EINVAL, "dbscan: %lld grid cells (max 2^26)", (long long)nc);
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int32_t *start = (int32_t *)ws;
-    ws += align256((size_t)(nc + 1) * 4);
-    double *cpts = (double *)ws;
-    ws += align256((size_t)n * 24);
-    int32_t *ids = (int32_t *)ws;
-    ws += align256((size_t)n * 4);
-    int32_t *parent = (int32_t *)ws;
-    ws += align256((size_t)n * 4);
-    uint8_t *core = (uint8_t *)ws;
-    ws += align256((size_t)n);
-    int32_t *changed = (int32_t *)ws;
-    ws += 256;
-    const PointGrid g = point_grid(origin, dims, eps, start, cpts, ids);     // cell edge = eps
-    int rc = nof_point_grid_build(points, n, origin, dims, eps, start, cpts, ids, ws, stream);
+    const DbscanWs ws(workspace, n, nc);
+    const PointGrid g = point_grid(origin, dims, eps, ws.start, ws.cpts, ws.ids);     // cell edge = eps
+    int rc = nof_point_grid_build(points, n, origin, dims, eps, ws.start, ws.cpts, ws.ids, ws.grid, stream);
     if (rc) return rc;
     const unsigned nb = div_up(n, 256);
-    hipLaunchKernelGGL(k_core_count, dim3(nb), dim3(256), 0, s, g, points, n, min_samples, core, parent);
+    hipLaunchKernelGGL(k_core_count, dim3(nb), dim3(256), 0, s, g, points, n, min_samples, ws.core, ws.parent);
     for (int round = 0; round < 64; ++round) {
         int32_t h = 0;
-        if (hipMemsetAsync(changed, 0, 4, s) != hipSuccess) return set_error(NOF_ELAUNCH, "dbscan: memset failed");
-        hipLaunchKernelGGL(k_hook, dim3(nb), dim3(256), 0, s, g, points, n, core, parent, changed);
-        hipLaunchKernelGGL(k_jump, dim3(nb), dim3(256), 0, s, n, parent);
-        if (hipMemcpyAsync(&h, changed, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        if (hipMemsetAsync(ws.changed, 0, 4, s) != hipSuccess) return set_error(NOF_ELAUNCH, "dbscan: memset failed");
+        hipLaunchKernelGGL(k_hook, dim3(nb), dim3(256), 0, s, g, points, n, ws.core, ws.parent, ws.changed);
+        hipLaunchKernelGGL(k_jump, dim3(nb), dim3(256), 0, s, n, ws.parent);
+        if (hipMemcpyAsync(&h, ws.changed, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return set_error(NOF_ELAUNCH, "dbscan: flag read-back failed");
         if (!h) break;
         if (round == 63) return set_error(NOF_ELAUNCH, "dbscan: union-find did not converge in 64 rounds");
     }
-    hipLaunchKernelGGL(k_label, dim3(nb), dim3(256), 0, s, g, points, n, core, parent, labels);
+    hipLaunchKernelGGL(k_label, dim3(nb), dim3(256), 0, s, g, points, n, ws.core, ws.parent, labels);
     return check_launch("dbscan");
 }
 

@@ -55,6 +55,7 @@
 // Tails: a row past L or S is staged as zeros; its K and V are zeroed like a masked row's and its
 // output is not written. There is no scalar path.
 #include "mfma_tile.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -389,27 +390,18 @@ __global__ void __launch_bounds__(FT_THREADS) k_ft_layer(const FtArgs a) {
         }
 }
 
-struct FtWs {
-    float *part;
+struct FtWs : Carver {
+    float *part, *ksum;
     h8v *kv;
-    float *ksum;
     int max_blk;
-};
-
-static size_t ft_carve(void *base, int32_t P, int32_t L, int32_t S, int32_t C, FtWs *ws) {
-    const size_t problems = 2 * (size_t)P;
-    const int max_blk = (int)div_up((uint64_t)(L > S ? L : S), FT_KV_ROWS);
-    const size_t n_part = align256(problems * max_blk * ((size_t)C * 32 + C) * 4);
-    const size_t n_kv = align256(problems * (size_t)C * 32 * 2), n_ksum = align256(problems * (size_t)C * 4);
-    char *b = static_cast<char *>(base);
-    if (ws) {
-        ws->part = (float *)b;
-        ws->kv = (h8v *)(b + n_part);
-        ws->ksum = (float *)(b + n_part + n_kv);
-        ws->max_blk = max_blk;
+    FtWs(void *base, int32_t P, int32_t L, int32_t S, int32_t C) : Carver(base) {
+        const size_t problems = 2 * (size_t)P;
+        max_blk = (int)div_up((uint64_t)(L > S ? L : S), FT_KV_ROWS);
+        part = take<float>(problems * max_blk * ((size_t)C * 32 + C));
+        kv = take<h8v>(problems * (size_t)C * 32 / 8);
+        ksum = take<float>(problems * (size_t)C);
     }
-    return n_part + n_kv + n_ksum;
-}
+};
 
 static size_t ft_layer_bytes(int32_t C) { return (size_t)20 * C * C + (size_t)16 * C; }
 
@@ -428,7 +420,7 @@ extern "C" {
 
 size_t nof_feature_transformer_workspace_bytes(int32_t P, int32_t L, int32_t S, int32_t C) {
     if (P < 1 || 2 * (int64_t)P > 65535 || L < 1 || S < 1 || (C != 128 && C != 256)) return 0;
-    return ft_carve(nullptr, P, L, S, C, nullptr);
+    return FtWs(nullptr, P, L, S, C).bytes;
 }
 
 int nof_feature_transformer(const nof_feature_transformer_desc *d, void *stream) {
@@ -443,23 +435,19 @@ int nof_feature_transformer(const nof_feature_transformer_desc *d, void *stream)
     for (int l = 0; l < d->n_layers; ++l)
         if (d->layer_kind[l] != NOF_FT_SELF && d->layer_kind[l] != NOF_FT_CROSS)
             return set_error(NOF_EINVAL, "%s: layer_kind[%d]=%d must be NOF_FT_SELF or NOF_FT_CROSS", fn, l, d->layer_kind[l]);
-    const struct { const void *p; const char *name; } ptrs[] = {
-        {d->feat_a, "feat_a"}, {d->feat_b, "feat_b"}, {d->weights, "weights"}, {d->workspace, "workspace"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->feat_a, "feat_a"}, {d->feat_b, "feat_b"}, {d->weights, "weights"},
+                                       {d->workspace, "workspace"}}))
+        return rc;
     if (((uintptr_t)d->feat_a | (uintptr_t)d->feat_b | (uintptr_t)d->weights | (uintptr_t)d->workspace) & 15)
         return set_error(NOF_EINVAL, "%s: feat_a, feat_b, weights and workspace must be 16-byte aligned", fn);
     const size_t lb = ft_layer_bytes(d->C);
     if (d->weights_bytes < lb * d->n_layers)
         return set_error(NOF_EINVAL, "%s: weights_bytes=%zu is below the %zu bytes of %d layers", fn, d->weights_bytes,
                          lb * d->n_layers, d->n_layers);
-    const size_t need = nof_feature_transformer_workspace_bytes(d->P, d->L, d->S, d->C);
-    if (d->workspace_bytes < need)
-        return set_error(NOF_EINVAL, "%s: workspace_bytes=%zu is below the %zu bytes needed", fn, d->workspace_bytes, need);
+    const FtWs ws(d->workspace, d->P, d->L, d->S, d->C);
+    if (int rc = require_workspace(fn, d->workspace_bytes, ws.bytes)) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    FtWs ws;
-    ft_carve(d->workspace, d->P, d->L, d->S, d->C, &ws);
     const int C = d->C;
     const FtSide aa{d->feat_a, d->feat_a, d->mask_a, d->mask_a, d->L, d->L};
     const FtSide bb{d->feat_b, d->feat_b, d->mask_b, d->mask_b, d->S, d->S};

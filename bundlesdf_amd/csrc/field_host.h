@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "field_core.h"
+#include "host_entry.h"
 
 namespace nof {
 

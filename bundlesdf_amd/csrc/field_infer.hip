@@ -72,19 +72,17 @@ extern "C" int nof_query_field(const void *table, int32_t table_dtype, const flo
 
 namespace {
 // the render's workspace: per-ray context records, then the per-tile records
-struct RenderWorkspace {
-    size_t rctx, rrec, total;
-    RenderWorkspace(int R, int S) {
-        size_t o = 0;
-        rctx = o; o += nof::align256((size_t)R * nof::RCTX * 4);
-        rrec = o; o += nof::align256((size_t)R * (S / 32) * nof::RREC * 4);
-        total = o;
+struct RenderWorkspace : nof::Carver {
+    float *rctx, *rrec;
+    RenderWorkspace(void *base, int R, int S) : Carver(base) {
+        rctx = take<float>((size_t)R * nof::RCTX);
+        rrec = take<float>((size_t)R * (S / 32) * nof::RREC);
     }
 };
 }  // namespace
 
 extern "C" size_t nof_render_workspace_bytes(int32_t R, int32_t S) {
-    return (R < 0 || S <= 0) ? 0 : RenderWorkspace(R, S).total;
+    return (R < 0 || S <= 0) ? 0 : RenderWorkspace(nullptr, R, S).bytes;
 }
 
 extern "C" int nof_render_rays(const nof_field_desc *d, const nof_render_out *o, void *stream) {
@@ -111,10 +109,9 @@ extern "C" int nof_render_rays(const nof_field_desc *d, const nof_render_out *o,
     nof::fill_sampling(a, d);
     nof::fill_model(a, d);
     a.perturb = 0;   // render_images renders with perturb=False: no draws are read
-    const RenderWorkspace ws(d->R, d->S);
-    char *w = (char *)o->workspace;
-    a.rctx = (float *)(w + ws.rctx);
-    const nof::RenderOut ro{o->rgb, o->depth, o->z, o->sdf, o->valid, (float *)(w + ws.rrec)};
+    const RenderWorkspace ws(o->workspace, d->R, d->S);
+    a.rctx = ws.rctx;
+    const nof::RenderOut ro{o->rgb, o->depth, o->z, o->sdf, o->valid, ws.rrec};
 
     hipStream_t st = (hipStream_t)stream;
     const int n_cu = nof::cu_count();
@@ -131,20 +128,18 @@ extern "C" int nof_render_rays(const nof_field_desc *d, const nof_render_out *o,
 
 namespace {
 // the surface render's workspace: per-ray records, the interval lists, the bracket records
-struct ViewWorkspace {
-    size_t vray, iv, brk, total;
-    ViewWorkspace(int n, int Kmax) {
-        size_t o = 0;
-        vray = o; o += nof::align256((size_t)n * nof::VRAY * 4);
-        iv = o; o += nof::align256((size_t)n * Kmax * 8);
-        brk = o; o += nof::align256((size_t)n * nof::VBRK * 4);
-        total = o;
+struct ViewWorkspace : nof::Carver {
+    float *vray, *iv, *brk;
+    ViewWorkspace(void *base, int n, int Kmax) : Carver(base) {
+        vray = take<float>((size_t)n * nof::VRAY);
+        iv = take<float>((size_t)n * Kmax * 2);
+        brk = take<float>((size_t)n * nof::VBRK);
     }
 };
 }  // namespace
 
 extern "C" size_t nof_render_view_workspace_bytes(int32_t n, int32_t Kmax) {
-    return (n < 0 || Kmax <= 0) ? 0 : ViewWorkspace(n, Kmax).total;
+    return (n < 0 || Kmax <= 0) ? 0 : ViewWorkspace(nullptr, n, Kmax).bytes;
 }
 
 extern "C" int nof_render_view(const nof_field_desc *d, const nof_view_desc *w, const nof_view_out *o, void *stream) {
@@ -179,8 +174,7 @@ extern "C" int nof_render_view(const nof_field_desc *d, const nof_view_desc *w, 
     nof::FieldArgs a{};
     nof::fill_model(a, d);
     a.n_ff = 0; a.ff = nullptr;   // the one frame's feature row travels in ViewArgs
-    const ViewWorkspace ws(w->n, d->Kmax);
-    char *wp = (char *)o->workspace;
+    const ViewWorkspace ws(o->workspace, w->n, d->Kmax);
     nof::ViewArgs v{};
     for (int i = 0; i < 12; ++i) v.c2w[i] = w->c2w[i];
     v.fx = w->K[0]; v.fy = w->K[4]; v.cx = w->K[2]; v.cy = w->K[5];
@@ -189,7 +183,7 @@ extern "C" int nof_render_view(const nof_field_desc *d, const nof_view_desc *w, 
     v.occ = w->occ; v.N = w->occ_n; v.Kmax = d->Kmax;
     v.n_ff = d->n_ff;
     v.ff = d->n_ff > 0 ? d->ff + (size_t)w->frame_id * d->n_ff : nullptr;
-    v.vray = (float *)(wp + ws.vray); v.iv = (float *)(wp + ws.iv); v.brk = (float *)(wp + ws.brk);
+    v.vray = ws.vray; v.iv = ws.iv; v.brk = ws.brk;
     v.t = o->t; v.depth = o->depth; v.normal = o->normal; v.rgb = o->rgb; v.hit = o->hit;
     v.index = o->index; v.tiles = o->tiles;
 

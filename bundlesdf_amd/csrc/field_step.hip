@@ -1573,24 +1573,35 @@ int launch_field(const nof::FieldArgs &a, int n_cu, hipStream_t st) {
     return NOF_OK;
 }
 
-struct FieldWorkspace {
-    size_t feat, dfeat, zbuf, tile_bwd, tile_sid, n_tiles, ray_aux, tile_aux, rctx, gmask, rrec, ctile, total;
-    FieldWorkspace(int R, int S, int mlp_dtype) {
+// The step's workspace: the size export reads `bytes`, nof_field_workspace_offsets `off`, the step the pointers.
+// part<I, T> is section I of NOF_WS_SECTIONS (include/nof.h names them in this order); the last is the total.
+struct FieldWorkspace : nof::Carver {
+    void *feat, *dfeat;
+    float *zbuf, *ray_aux, *rctx, *rrec;
+    uint8_t *tile_bwd;
+    int *tile_sid, *n_tiles, *ctile;
+    float4 *tile_aux;
+    uint32_t *gmask;
+    uint64_t off[NOF_WS_SECTIONS] = {};
+    template <int I, typename T> T *part(size_t count) {
+        static_assert(I < NOF_WS_SECTIONS - 1, "a new section needs a larger NOF_WS_SECTIONS in include/nof.h");
+        return off[I] = bytes, take<T>(count);
+    }
+    FieldWorkspace(void *base, int R, int S, int mlp_dtype) : Carver(base) {
         const size_t el = mlp_dtype == NOF_F16 ? 2 : 4, n = (size_t)R * S, nt = (size_t)R * (S / 32);
-        size_t o = 0;
-        feat = o; o += nof::align256(n * 32 * el);
-        dfeat = o; o += nof::align256(n * 32 * el);
-        zbuf = o; o += nof::align256(n * 4);
-        tile_bwd = o; o += nof::align256(nt);
-        tile_sid = o; o += nof::align256(nt * 4);
-        n_tiles = o; o += nof::align256(4 * nof::LOSS_ZERO_WORDS);   // + the loss rows (folded by the scatter kernel)
-        ray_aux = o; o += nof::align256((size_t)R * nof::RAY_AUX * 4);
-        tile_aux = o; o += nof::align256(nt * nof::TILE_AUX * 16);
-        rctx = o; o += nof::align256((size_t)R * nof::RCTX * 4);
-        gmask = o; o += nof::align256(nt * 4);
-        rrec = o; o += nof::align256(nt * nof::TREC * 4);
-        ctile = o; o += nof::align256(nt * 4);
-        total = o;
+        feat = part<0, char>(n * 32 * el);
+        dfeat = part<1, char>(n * 32 * el);
+        zbuf = part<2, float>(n);
+        tile_bwd = part<3, uint8_t>(nt);
+        tile_sid = part<4, int>(nt);
+        n_tiles = part<5, int>(nof::LOSS_ZERO_WORDS);   // + the loss rows (folded by the scatter kernel)
+        ray_aux = part<6, float>((size_t)R * nof::RAY_AUX);
+        tile_aux = part<7, float4>(nt * nof::TILE_AUX);
+        rctx = part<8, float>((size_t)R * nof::RCTX);
+        gmask = part<9, uint32_t>(nt);
+        rrec = part<10, float>(nt * nof::TREC);
+        ctile = part<11, int>(nt);
+        off[NOF_WS_SECTIONS - 1] = bytes;
     }
 };
 // the encode's xy-quad mirror: amp, batches large enough to repay its per-step rebuild (~25 us)
@@ -1601,23 +1612,22 @@ bool quads_on(const nof_field_desc *d) {
 }  // namespace
 
 extern "C" size_t nof_field_workspace_bytes(int32_t R, int32_t S, int32_t mlp_dtype) {
-    return FieldWorkspace(R, S, mlp_dtype).total;
+    return FieldWorkspace(nullptr, R, S, mlp_dtype).bytes;
 }
 
 extern "C" int nof_field_workspace_offsets(int32_t R, int32_t S, int32_t mlp_dtype, uint64_t *offsets, int32_t n) {
     if (R < 0 || S <= 0 || !offsets || n < NOF_WS_SECTIONS)
         return nof::set_error(NOF_EINVAL, "field_workspace_offsets: bad R=%d S=%d or n=%d < %d", R, S, n,
                               NOF_WS_SECTIONS);
-    const FieldWorkspace w(R, S, mlp_dtype);
-    const size_t o[NOF_WS_SECTIONS] = {w.feat, w.dfeat, w.zbuf, w.tile_bwd, w.tile_sid, w.n_tiles, w.ray_aux,
-                                       w.tile_aux, w.rctx, w.gmask, w.rrec, w.ctile, w.total};
-    for (int i = 0; i < NOF_WS_SECTIONS; ++i) offsets[i] = o[i];
+    const FieldWorkspace w(nullptr, R, S, mlp_dtype);
+    for (int i = 0; i < NOF_WS_SECTIONS; ++i) offsets[i] = w.off[i];
     return NOF_OK;
 }
 
 extern "C" size_t nof_field_desc_size(void) { return sizeof(nof_field_desc); }
 
 extern "C" int nof_quad_mirror(const nof_field_desc *d, void *stream) {
+    if (!d) return nof::set_error(NOF_EINVAL, "quad_mirror: desc is NULL");
     if (d->L > 16 || d->C != 2)
         return nof::set_error(NOF_EINVAL, "quad_mirror: needs C=2, L<=16 (got %u,%u)", d->C, d->L);
     if (d->R <= 0 || !quads_on(d)) return NOF_OK;   // the step would not read the mirror
@@ -1630,6 +1640,7 @@ extern "C" int nof_quad_mirror(const nof_field_desc *d, void *stream) {
 }
 
 extern "C" int nof_field_step(const nof_field_desc *d, void *stream) {
+    if (!d) return nof::set_error(NOF_EINVAL, "field_step: desc is NULL");
     if (d->S % 32 != 0 || d->S > 320 || d->N_oct + d->N_dep != d->S)
         return nof::set_error(NOF_EINVAL, "field_step: S=%d must be N_oct+N_dep, a multiple of 32, <= 320", d->S);
     if (int rc = nof::check_geometry("field_step", d, false)) return rc;
@@ -1691,23 +1702,11 @@ extern "C" int nof_field_step(const nof_field_desc *d, void *stream) {
     a.ray_grad = d->ray_grad; a.loss_acc = d->loss_acc; a.dbg_z = d->dbg_z; a.dbg_raw = d->dbg_raw;
     a.dbg_valid = d->dbg_valid; a.dbg_rgb = d->dbg_rgb; a.ablate = d->ablate;
     a.slot_mask = (uint32_t)slots - 1;
-    {
-        char *w = (char *)d->workspace;
-        const FieldWorkspace ws(d->R, d->S, d->mlp_dtype);
-        a.feat = w + ws.feat;
-        a.dfeat = w + ws.dfeat;
-        a.zbuf = (float *)(w + ws.zbuf);
-        a.tile_bwd = (uint8_t *)(w + ws.tile_bwd);
-        a.tile_sid = (int *)(w + ws.tile_sid);
-        a.n_tiles = (int *)(w + ws.n_tiles);
-        a.loss_part = (float *)(w + ws.n_tiles) + 16;
-        a.ray_aux = (float *)(w + ws.ray_aux);
-        a.tile_aux = (float4 *)(w + ws.tile_aux);
-        a.rctx = (float *)(w + ws.rctx);
-        a.tile_gmask = (uint32_t *)(w + ws.gmask);
-        a.rrec = (float *)(w + ws.rrec);
-        a.ctile_list = (int *)(w + ws.ctile);
-    }
+    const FieldWorkspace ws(d->workspace, d->R, d->S, d->mlp_dtype);
+    a.feat = ws.feat; a.dfeat = ws.dfeat; a.zbuf = ws.zbuf; a.tile_bwd = ws.tile_bwd; a.tile_sid = ws.tile_sid;
+    a.n_tiles = ws.n_tiles; a.loss_part = (float *)ws.n_tiles + 16;   // the loss rows follow the counters in their part
+    a.ray_aux = ws.ray_aux; a.tile_aux = ws.tile_aux; a.rctx = ws.rctx; a.tile_gmask = ws.gmask; a.rrec = ws.rrec;
+    a.ctile_list = ws.ctile;
 
     hipStream_t st = (hipStream_t)stream;
     const int n_cu = nof::cu_count();

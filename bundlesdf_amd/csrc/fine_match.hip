@@ -47,6 +47,7 @@
 // (k_fine_windows also the frame against N) before it forms an address. A row that fails is written as
 // zeros (context, window and expec alike) and nothing is read for it.
 #include "mfma_tile.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -305,14 +306,12 @@ int nof_fine_windows(const nof_fine_windows_desc *d, void *stream) {
             return set_error(NOF_EINVAL, "%s: stride %s=%lld must be at most %d", fn, g.name, (long long)g.v * d->stride,
                              FM_MAX_SIDE);
     }
-    if (d->weights_bytes < fm_weight_bytes())
-        return set_error(NOF_EINVAL, "%s: weights_bytes=%zu is below the %zu bytes needed", fn, d->weights_bytes,
-                         fm_weight_bytes());
-    const struct { const void *p; const char *name; } ptrs[] = {
+    if (int rc = require_workspace(fn, d->weights_bytes, fm_weight_bytes(), "weights_bytes")) return rc;
+    const NamedPointer ptrs[] = {
         {d->fine_a, "fine_a"}, {d->fine_b, "fine_b"}, {d->coarse_a, "coarse_a"}, {d->coarse_b, "coarse_b"},
         {d->weights, "weights"}, {d->context, "context"}, {d->win_a, "win_a"}, {d->win_b, "win_b"}};
-    for (const auto &a : ptrs) {
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    for (const NamedPointer &a : ptrs) {   // each pointer's alignment is judged before the next one's presence
+        if (int rc = require_pointers(fn, {a})) return rc;
         if ((uintptr_t)a.p & 15) return set_error(NOF_EINVAL, "%s: %s must be 16-byte aligned", fn, a.name);
     }
     if (d->M == 0) return NOF_OK;
@@ -348,9 +347,7 @@ int nof_fine_expectation(const nof_fine_expectation_desc *d, void *stream) {
     if (int rc = fm_indices(fn, d->M, d->P, d->pair, d->i, d->j)) return rc;
     if (d->L < 1) return set_error(NOF_EINVAL, "%s: L=%d must be at least 1", fn, d->L);
     if (d->S < 1) return set_error(NOF_EINVAL, "%s: S=%d must be at least 1", fn, d->S);
-    const struct { const void *p; const char *name; } ptrs[] = {{d->win_a, "win_a"}, {d->win_b, "win_b"}, {d->expec, "expec"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->win_a, "win_a"}, {d->win_b, "win_b"}, {d->expec, "expec"}})) return rc;
     if (((uintptr_t)d->win_a | (uintptr_t)d->win_b) & 15)
         return set_error(NOF_EINVAL, "%s: win_a and win_b must be 16-byte aligned", fn);
     if (d->M == 0) return NOF_OK;

@@ -64,6 +64,7 @@
 // is neither bad nor usable, while an invalid tap inside the image is staged as 0. geometry stages
 // the tile with a halo of one pixel.
 #include "geom_device.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -405,11 +406,9 @@ int nof_frame_geometry(const nof_frame_geometry_desc *d, void *stream) {
     const char *fn = "frame_geometry";
     if (!d) return set_error(NOF_EINVAL, "%s: desc is NULL", fn);
     if (int rc = fm_check_shape(fn, d->N, d->H, d->W)) return rc;
-    const struct { const void *p; const char *name; } ptrs[] = {
-        {d->depth_in, "depth_in"}, {d->K, "K"}, {d->depth, "depth"}, {d->points, "points"}, {d->normals, "normals"},
-        {d->n_valid, "n_valid"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->depth_in, "depth_in"}, {d->K, "K"}, {d->depth, "depth"}, {d->points, "points"},
+                                       {d->normals, "normals"}, {d->n_valid, "n_valid"}}))
+        return rc;
     if (d->depth_in == d->depth) return set_error(NOF_EINVAL, "%s: depth_in and depth are the same buffer", fn);
     if (d->depth_min != d->depth_min || d->z_diff != d->z_diff || d->sin_edge != d->sin_edge)
         return set_error(NOF_EINVAL, "%s: depth_min, z_diff or sin_edge is NaN", fn);
@@ -434,13 +433,12 @@ int nof_frame_lift_matches(const nof_frame_lift_desc *d, void *stream) {
     if (d->gate_normal && d->cos_normal != d->cos_normal) return set_error(NOF_EINVAL, "%s: cos_normal is NaN", fn);
     if (d->depth_min != d->depth_min) return set_error(NOF_EINVAL, "%s: depth_min is NaN", fn);
     const bool rows = d->M > 0;
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {d->points, "points", true}, {d->normals, "normals", true}, {d->pair_frames, "pair_frames", true},
-        {d->pair_start, "pair_start", true}, {d->uv_a, "uv_a", rows}, {d->uv_b, "uv_b", rows}, {d->pts_a, "pts_a", rows},
-        {d->pts_b, "pts_b", rows}, {d->normals_a, "normals_a", rows}, {d->normals_b, "normals_b", rows},
-        {d->valid, "valid", rows}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->points, "points"}, {d->normals, "normals"}, {d->pair_frames, "pair_frames"},
+                                       {d->pair_start, "pair_start"}, {d->uv_a, "uv_a", rows}, {d->uv_b, "uv_b", rows},
+                                       {d->pts_a, "pts_a", rows}, {d->pts_b, "pts_b", rows},
+                                       {d->normals_a, "normals_a", rows}, {d->normals_b, "normals_b", rows},
+                                       {d->valid, "valid", rows}}))
+        return rc;
     if (!rows) return NOF_OK;
     hipLaunchKernelGGL(k_frame_lift, dim3(div_up((uint64_t)d->M, 256)), dim3(256), 0, (hipStream_t)stream, *d);
     return check_launch(fn);
@@ -454,11 +452,9 @@ int nof_frame_covisibility(const nof_frame_covis_desc *d, void *stream) {
     if (d->stride < 1) return set_error(NOF_EINVAL, "%s: stride=%d must be at least 1", fn, d->stride);
     if (d->depth_min != d->depth_min || d->cos_visible != d->cos_visible)
         return set_error(NOF_EINVAL, "%s: depth_min or cos_visible is NaN", fn);
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {d->points, "points", true}, {d->normals, "normals", true}, {d->pairs, "pairs", d->Q > 0}, {d->T, "T", d->Q > 0},
-        {d->counts, "counts", d->Q > 0}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->points, "points"}, {d->normals, "normals"}, {d->pairs, "pairs", d->Q > 0},
+                                       {d->T, "T", d->Q > 0}, {d->counts, "counts", d->Q > 0}}))
+        return rc;
     if (d->Q == 0) return NOF_OK;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d->counts, 0, sizeof(int32_t) * 2 * (size_t)d->Q, s) != hipSuccess)

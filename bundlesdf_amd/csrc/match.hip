@@ -39,6 +39,7 @@
 // staged as zeros (C is a multiple of 8, the chunk of one lane); there is no scalar path. No
 // floating-point atomics, no reduction whose order depends on scheduling.
 #include "mfma_tile.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -222,24 +223,17 @@ __global__ void __launch_bounds__(256) k_match_emit(const int32_t *row_best, con
     if (threadIdx.x == 0) n_matches[p] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
 }
 
-struct MatchWs {
+struct MatchWs : Carver {
     float *row_max, *row_sum, *col_max, *col_sum, *row_conf;
     int32_t *row_best, *col_best;
-};
-
-static size_t match_carve(void *base, int32_t P, int32_t L, int32_t S, MatchWs *ws) {
-    const size_t nl = align256((size_t)P * L * 4), ns = align256((size_t)P * S * 4);
-    char *b = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) { char *q = b ? b + off : nullptr; off += n; return q; };
-    char *parts[7] = {take(nl), take(nl), take(ns), take(ns), take(nl), take(nl), take(ns)};
-    if (ws) {
-        ws->row_max = (float *)parts[0]; ws->row_sum = (float *)parts[1]; ws->col_max = (float *)parts[2];
-        ws->col_sum = (float *)parts[3]; ws->row_conf = (float *)parts[4]; ws->row_best = (int32_t *)parts[5];
-        ws->col_best = (int32_t *)parts[6];
+    MatchWs(void *base, int32_t P, int32_t L, int32_t S) : Carver(base) {
+        const size_t nl = (size_t)P * L, ns = (size_t)P * S;
+        row_max = take<float>(nl); row_sum = take<float>(nl);
+        col_max = take<float>(ns); col_sum = take<float>(ns);
+        row_conf = take<float>(nl); row_best = take<int32_t>(nl);
+        col_best = take<int32_t>(ns);
     }
-    return off;
-}
+};
 
 template <bool BEST>
 static void match_launch(const MatchSide &side, int P, hipStream_t s) {
@@ -257,7 +251,7 @@ extern "C" {
 
 size_t nof_match_workspace_bytes(int32_t P, int32_t L, int32_t S) {
     if (P < 1 || L < 1 || S < 1) return 0;
-    return match_carve(nullptr, P, L, S, nullptr);
+    return MatchWs(nullptr, P, L, S).bytes;
 }
 
 int nof_match_descriptors(const nof_match_desc *d, void *stream) {
@@ -279,20 +273,15 @@ int nof_match_descriptors(const nof_match_desc *d, void *stream) {
     if ((d->valid_a == nullptr) != (d->valid_b == nullptr))
         return set_error(NOF_EINVAL, "%s: %s is NULL while the other side's mask is given", fn,
                          d->valid_a ? "valid_b" : "valid_a");
-    const struct { const void *p; const char *name; } ptrs[] = {
-        {d->desc_a, "desc_a"}, {d->desc_b, "desc_b"}, {d->workspace, "workspace"}, {d->j_of_i, "j_of_i"},
-        {d->conf, "conf"}, {d->n_matches, "n_matches"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->desc_a, "desc_a"}, {d->desc_b, "desc_b"}, {d->workspace, "workspace"},
+                                       {d->j_of_i, "j_of_i"}, {d->conf, "conf"}, {d->n_matches, "n_matches"}}))
+        return rc;
     if (((uintptr_t)d->desc_a | (uintptr_t)d->desc_b) & 15)
         return set_error(NOF_EINVAL, "%s: desc_a and desc_b must be 16-byte aligned", fn);
-    const size_t need = nof_match_workspace_bytes(d->P, d->L, d->S);
-    if (d->workspace_bytes < need)
-        return set_error(NOF_EINVAL, "%s: workspace_bytes=%zu is below the %zu bytes needed", fn, d->workspace_bytes, need);
+    MatchWs ws(d->workspace, d->P, d->L, d->S);
+    if (int rc = require_workspace(fn, d->workspace_bytes, ws.bytes)) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    MatchWs ws;
-    match_carve(d->workspace, d->P, d->L, d->S, &ws);
     if (d->row_max) ws.row_max = d->row_max;
     if (d->row_sum) ws.row_sum = d->row_sum;
     if (d->col_max) ws.col_max = d->col_max;

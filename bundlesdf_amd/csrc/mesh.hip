@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "geom_device.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -222,11 +223,9 @@ int nof_marching_cubes_count(const float *volume, int32_t n0, int32_t n1, int32_
     int64_t P;
     if (int rc = mc_shape(fn, n0, n1, n2, &P)) return rc;
     if (!std::isfinite(level)) return set_error(NOF_EINVAL, "%s: level=%g must be finite", fn, (double)level);
-    const struct { const void *p; const char *name; } ptrs[] = {{volume, "volume"}, {tables, "tables"}, {cells, "cells"},
-                                                                {block_counts, "block_counts"},
-                                                                {block_range, "block_range"}};
-    for (const auto &a : ptrs)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{volume, "volume"}, {tables, "tables"}, {cells, "cells"},
+                                       {block_counts, "block_counts"}, {block_range, "block_range"}}))
+        return rc;
     hipLaunchKernelGGL(k_mc_count, dim3(div_up(P, MC_BLOCK)), dim3(MC_BLOCK), 0, (hipStream_t)stream, volume, n0, n1, n2,
                        (int)P, level, tables, cells, block_counts, block_range);
     return check_launch(fn);
@@ -241,11 +240,9 @@ int nof_marching_cubes_emit(const float *volume, int32_t n0, int32_t n1, int32_t
     if (!std::isfinite(level)) return set_error(NOF_EINVAL, "%s: level=%g must be finite", fn, (double)level);
     if (n_vertices < 0 || n_vertices > 3 * P) return set_error(NOF_EINVAL, "%s: n_vertices=%lld must be in [0, 3 points]", fn, (long long)n_vertices);
     if (n_faces < 0 || n_faces > 5 * P) return set_error(NOF_EINVAL, "%s: n_faces=%lld must be in [0, 5 points]", fn, (long long)n_faces);
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {volume, "volume", true}, {tables, "tables", true}, {cells, "cells", true}, {block_base, "block_base", true},
-        {vertices, "vertices", n_vertices > 0}, {faces, "faces", n_faces > 0}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{volume, "volume"}, {tables, "tables"}, {cells, "cells"}, {block_base, "block_base"},
+                                       {vertices, "vertices", n_vertices > 0}, {faces, "faces", n_faces > 0}}))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n_vertices > 0)
         hipLaunchKernelGGL(k_mc_vertices, dim3(div_up(P, MC_BLOCK)), dim3(MC_BLOCK), 0, s, volume, n1, n2, (int)P, level,

@@ -35,6 +35,7 @@
 // All of it is IEEE f64 + - * / sqrt in the stated order with contraction off; tests/mesh_render_oracle.py
 // restates steps 2-8 in numpy and the z-buffer is oracle/texture.py's raster.
 #include "raster.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -238,12 +239,10 @@ int nof_render_mesh(const nof_mesh_render_desc *d, void *stream) {
         if (d->tex_h < 1 || d->tex_w < 1)
             return set_error(NOF_EINVAL, "%s: tex_h=%d, tex_w=%d must be positive", fn, d->tex_h, d->tex_w);
     }
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {d->vertices, "vertices", d->n_faces > 0}, {d->faces, "faces", d->n_faces > 0}, {d->ob_in_cam, "ob_in_cam", true},
-        {d->K, "K", true}, {d->workspace, "workspace", true}, {d->depth, "depth", true}, {d->face, "face", true},
-        {d->rgb, "rgb", true}, {d->normal, "normal", true}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->vertices, "vertices", d->n_faces > 0}, {d->faces, "faces", d->n_faces > 0},
+                                       {d->ob_in_cam, "ob_in_cam"}, {d->K, "K"}, {d->workspace, "workspace"},
+                                       {d->depth, "depth"}, {d->face, "face"}, {d->rgb, "rgb"}, {d->normal, "normal"}}))
+        return rc;
     const Pinhole c = {d->K[0], d->K[4], d->K[2], d->K[5]};
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_pixels = (int64_t)d->B * d->H * d->W, n_items = (int64_t)d->B * d->n_faces;

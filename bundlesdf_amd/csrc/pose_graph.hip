@@ -62,6 +62,7 @@
 #include <math.h>
 
 #include "geom_device.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -528,36 +529,28 @@ __global__ __launch_bounds__(256) void k_pg_solve(int32_t N, int32_t n_inner, in
     }
 }
 
-struct PgPlan {
-    int32_t sp_chunks, dn_chunks;
-    size_t off_cnt, off_sp, off_dn, off_A, off_g, off_totals, bytes;
-};
-
 // The workspace: T [N,16] f64 | cnt [N] i32 | sp_part [P, sp_chunks, 92] f64 | dn_part [N (N - 1) / 2,
-// dn_chunks, 29] f64 | A [6N,6N] f64 | g [6N] f64 | totals [4] f64, each part aligned to 256 bytes.
-static PgPlan pg_plan(int32_t N, int32_t P, int64_t M, int32_t H, int32_t W) {
-    PgPlan pl;
-    const uint64_t mean_tiles = P > 0 ? div_up((uint64_t)(M > 0 ? M : 0), (uint64_t)P * PG_TILE) : 0;
-    pl.sp_chunks = P > 0 ? (int32_t)(2 * mean_tiles < 1 ? 1 : (2 * mean_tiles > PG_SP_MAX_CHUNKS ? PG_SP_MAX_CHUNKS : 2 * mean_tiles)) : 0;
-    const uint64_t tiles = (H > 0 && W > 0) ? div_up((uint64_t)H * (uint64_t)W, PG_TILE) : 0;
-    pl.dn_chunks = (int32_t)(tiles > PG_DN_MAX_CHUNKS ? PG_DN_MAX_CHUNKS : tiles);
-    const size_t n = 6 * (size_t)N;
-    size_t at = align256((size_t)N * 16 * sizeof(double));
-    pl.off_cnt = at;
-    at += align256((size_t)N * sizeof(int32_t));
-    pl.off_sp = at;
-    at += align256((size_t)P * pl.sp_chunks * PG_SP * sizeof(double));
-    pl.off_dn = at;
-    at += align256((size_t)N * (N - 1) / 2 * pl.dn_chunks * PG_DN * sizeof(double));
-    pl.off_A = at;
-    at += align256(n * n * sizeof(double));
-    pl.off_g = at;
-    at += align256(n * sizeof(double));
-    pl.off_totals = at;
-    at += align256(4 * sizeof(double));
-    pl.bytes = at;
-    return pl;
-}
+// dn_chunks, 29] f64 | A [6N,6N] f64 | g [6N] f64 | totals [4] f64, each part aligned to 256 bytes. The
+// size export reads `bytes` of a null base, the entry point the pointers into the caller's buffer.
+struct PgPlan : Carver {
+    int32_t sp_chunks, dn_chunks;
+    double *T, *sp_part, *dn_part, *A, *g, *totals;
+    int32_t *cnt;
+    PgPlan(void *base, int32_t N, int32_t P, int64_t M, int32_t H, int32_t W) : Carver(base) {
+        const uint64_t mean_tiles = P > 0 ? div_up((uint64_t)(M > 0 ? M : 0), (uint64_t)P * PG_TILE) : 0;
+        sp_chunks = P > 0 ? (int32_t)(2 * mean_tiles < 1 ? 1 : (2 * mean_tiles > PG_SP_MAX_CHUNKS ? PG_SP_MAX_CHUNKS : 2 * mean_tiles)) : 0;
+        const uint64_t tiles = (H > 0 && W > 0) ? div_up((uint64_t)H * (uint64_t)W, PG_TILE) : 0;
+        dn_chunks = (int32_t)(tiles > PG_DN_MAX_CHUNKS ? PG_DN_MAX_CHUNKS : tiles);
+        const size_t n = 6 * (size_t)N;
+        T = take<double>((size_t)N * 16);
+        cnt = take<int32_t>((size_t)N);
+        sp_part = take<double>((size_t)P * sp_chunks * PG_SP);
+        dn_part = take<double>((size_t)N * (N - 1) / 2 * dn_chunks * PG_DN);
+        A = take<double>(n * n);
+        g = take<double>(n);
+        totals = take<double>(4);
+    }
+};
 
 }  // namespace nof
 
@@ -567,7 +560,7 @@ extern "C" {
 
 size_t nof_pose_graph_workspace_bytes(int32_t N, int32_t P, int64_t M, int32_t H, int32_t W) {
     if (N < 1 || N > PG_MAX_FRAMES || P < 0 || M < 0 || H < 0 || W < 0 || (int64_t)H * W >= (1ll << 24)) return 0;
-    return pg_plan(N, P, M, H, W).bytes;
+    return PgPlan(nullptr, N, P, M, H, W).bytes;
 }
 
 int nof_pose_graph_optimize(const nof_pose_graph_desc *d, void *stream) {
@@ -583,10 +576,9 @@ int nof_pose_graph_optimize(const nof_pose_graph_desc *d, void *stream) {
     if (!(d->robust_delta > 0)) return set_error(NOF_EINVAL, "%s: robust_delta=%g must be positive", fn, d->robust_delta);
     if (sparse) {
         if (!(d->w_sparse >= 0)) return set_error(NOF_EINVAL, "%s: w_sparse=%g must not be negative", fn, d->w_sparse);
-        const struct { const void *p; const char *name; } ptrs[] = {{d->pair_frames, "pair_frames"}, {d->pair_start, "pair_start"}};
-        for (const auto &a : ptrs)
-            if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
-        if (d->M > 0 && (!d->pts_a || !d->pts_b)) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, d->pts_a ? "pts_b" : "pts_a");
+        if (int rc = require_pointers(fn, {{d->pair_frames, "pair_frames"}, {d->pair_start, "pair_start"},
+                                           {d->pts_a, "pts_a", d->M > 0}, {d->pts_b, "pts_b", d->M > 0}}))
+            return rc;
     }
     if (dense) {
         if (!d->points || !d->normals)
@@ -603,21 +595,16 @@ int nof_pose_graph_optimize(const nof_pose_graph_desc *d, void *stream) {
         if (!(d->fx == d->fx && d->fy == d->fy && d->cx == d->cx && d->cy == d->cy))
             return set_error(NOF_EINVAL, "%s: fx, fy, cx or cy is NaN", fn);
     }
-    const struct { const void *p; const char *name; } need[] = {{d->poses, "poses"}, {d->fixed, "fixed"},
-        {d->poses_out, "poses_out"}, {d->history, "history"}, {d->workspace, "workspace"}};
-    for (const auto &a : need)
-        if (!a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{d->poses, "poses"}, {d->fixed, "fixed"}, {d->poses_out, "poses_out"},
+                                       {d->history, "history"}, {d->workspace, "workspace"}}))
+        return rc;
     const int32_t N = d->N, n = 6 * N, P = d->P, H = dense ? d->H : 0, W = dense ? d->W : 0;
-    const PgPlan pl = pg_plan(N, P, d->M, H, W);
-    if (d->workspace_bytes < pl.bytes)
-        return set_error(NOF_EINVAL, "%s: workspace_bytes=%zu is below the %zu bytes needed", fn, d->workspace_bytes, pl.bytes);
+    const PgPlan pl(d->workspace, N, P, d->M, H, W);
+    if (int rc = require_workspace(fn, d->workspace_bytes, pl.bytes)) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)d->workspace;
-    double *T = (double *)ws;
-    int32_t *cnt = (int32_t *)(ws + pl.off_cnt);
-    double *sp_part = (double *)(ws + pl.off_sp), *dn_part = (double *)(ws + pl.off_dn);
-    double *A = (double *)(ws + pl.off_A), *g = (double *)(ws + pl.off_g), *totals = (double *)(ws + pl.off_totals);
+    double *T = pl.T, *sp_part = pl.sp_part, *dn_part = pl.dn_part, *A = pl.A, *g = pl.g, *totals = pl.totals;
+    int32_t *cnt = pl.cnt;
     const int32_t HW = H * W;
     PgDense dd;
     dd.points = d->points, dd.normals = d->normals;

@@ -22,6 +22,7 @@
 //                       flags, their count, min_inliers, and the 17 sums in a fixed
 //                       thread -> row assignment and a fixed order of additions.
 #include "geom_device.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -394,16 +395,17 @@ __global__ __launch_bounds__(256) void k_ransac_flags(const double *__restrict__
     }
 }
 
-static size_t ransac_trials(int32_t P, int32_t T) { return (size_t)P * (size_t)T; }
-
-static RansacWs ransac_carve(void *workspace, int32_t P, int32_t T) {
-    const size_t pt = ransac_trials(P, T);
-    RansacWs ws;
-    ws.pose = (double *)workspace;
-    ws.score = (int64_t *)(ws.pose + pt * 12);
-    ws.live = (uint8_t *)(ws.score + pt);
-    return ws;
-}
+// One part: the three arrays lie packed in it, and only their sum is rounded up.
+struct RansacPlan : Carver {
+    RansacWs ws{};
+    RansacPlan(void *base, int32_t P, int32_t T) : Carver(base) {
+        const size_t pt = (size_t)P * (size_t)T;
+        ws.pose = (double *)take<char>(pt * (12 * sizeof(double) + sizeof(int64_t) + 1));
+        if (!base) return;
+        ws.score = (int64_t *)(ws.pose + pt * 12);
+        ws.live = (uint8_t *)(ws.score + pt);
+    }
+};
 
 }  // namespace nof
 
@@ -414,8 +416,7 @@ extern "C" {
 size_t nof_ransac_workspace_bytes(int32_t P, int64_t M, int32_t n_trials) {
     (void)M;    // nothing is kept per row
     if (P < 1 || n_trials < 1) return 0;
-    const size_t pt = ransac_trials(P, n_trials);
-    return align256(pt * (12 * sizeof(double) + sizeof(int64_t) + 1));
+    return RansacPlan(nullptr, P, n_trials).bytes;
 }
 
 int nof_ransac_pairs(const nof_ransac_desc *d, void *stream) {
@@ -432,22 +433,20 @@ int nof_ransac_pairs(const nof_ransac_desc *d, void *stream) {
     if (!(d->inlier_dist_sq >= 0))
         return set_error(NOF_EINVAL, "%s: inlier_dist_sq=%g must not be negative", fn, d->inlier_dist_sq);
     if (d->normals_a && d->cos_normal != d->cos_normal) return set_error(NOF_EINVAL, "%s: cos_normal is NaN", fn);
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {d->best_trial, "best_trial", true}, {d->score, "score", true}, {d->pose, "pose", true},
-        {d->n_inliers, "n_inliers", true}, {d->sums, "sums", true}, {d->inlier, "inlier", d->M > 0},
-        {d->pts_a, "pts_a", d->M > 0}, {d->pts_b, "pts_b", d->M > 0}, {d->pair_start, "pair_start", d->M > 0},
-        {d->max_trans_sq, "max_trans_sq", d->M > 0}, {d->min_trace, "min_trace", d->M > 0},
-        {d->workspace, "workspace", d->M > 0}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    const bool rows = d->M > 0;
+    if (int rc = require_pointers(fn, {{d->best_trial, "best_trial"}, {d->score, "score"}, {d->pose, "pose"},
+                                       {d->n_inliers, "n_inliers"}, {d->sums, "sums"}, {d->inlier, "inlier", rows},
+                                       {d->pts_a, "pts_a", rows}, {d->pts_b, "pts_b", rows},
+                                       {d->pair_start, "pair_start", rows}, {d->max_trans_sq, "max_trans_sq", rows},
+                                       {d->min_trace, "min_trace", rows}, {d->workspace, "workspace", rows}}))
+        return rc;
     if (d->M == 0) return NOF_OK;
-    const size_t need = nof_ransac_workspace_bytes(d->P, d->M, d->n_trials);
-    if (d->workspace_bytes < need)
-        return set_error(NOF_EINVAL, "%s: workspace_bytes=%zu is below the %zu bytes needed", fn, d->workspace_bytes, need);
+    const int32_t P = d->P, T = d->n_trials;
+    const RansacPlan pl(d->workspace, P, T);
+    if (int rc = require_workspace(fn, d->workspace_bytes, pl.bytes)) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    const int32_t P = d->P, T = d->n_trials;
-    const RansacWs ws = ransac_carve(d->workspace, P, T);
+    const RansacWs ws = pl.ws;
     uint32_t seed_hash = d->seed;                            // ransac_hash on the host
     seed_hash ^= seed_hash >> 16;
     seed_hash *= 0x7feb352du;

@@ -20,6 +20,7 @@
 // rays, dtype=float) does.
 #include "nof_device.h"
 #include "ray_trace.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -355,16 +356,38 @@ __global__ __launch_bounds__(256) void k_grid_fill(const double *__restrict__ pt
     }
 }
 
+struct PoolWs : Carver {
+    uint8_t *hrow, *dil, *flag;
+    float *nearfar;
+    int32_t *blk_count;
+    int64_t *blk_off;
+    size_t nblk;
+    PoolWs(void *base, int32_t F, int32_t H, int32_t W) : Carver(base) {
+        const size_t P = (size_t)F * H * W;
+        nblk = (P + POOL_BLOCK - 1) / POOL_BLOCK;
+        hrow = take<uint8_t>(P); dil = take<uint8_t>(P); flag = take<uint8_t>(P);
+        nearfar = take<float>(P * 2);
+        blk_count = take<int32_t>(nblk);
+        blk_off = take<int64_t>(nblk + 1);
+    }
+};
+
+struct GridWs : Carver {
+    int32_t *count, *cursor;
+    int64_t *start;
+    GridWs(void *base, int64_t n_cells) : Carver(base) {
+        count = take<int32_t>((size_t)n_cells); cursor = take<int32_t>((size_t)n_cells);
+        start = take<int64_t>((size_t)(n_cells + 1));
+    }
+};
+
 }  // namespace nof
 
 using namespace nof;
 
 extern "C" {
 
-size_t nof_ray_pool_workspace_bytes(int32_t F, int32_t H, int32_t W) {
-    const size_t P = (size_t)F * H * W, nblk = (P + POOL_BLOCK - 1) / POOL_BLOCK;
-    return align256(P) * 3 + align256(P * 8) + align256(nblk * 4) + align256((nblk + 1) * 8);
-}
+size_t nof_ray_pool_workspace_bytes(int32_t F, int32_t H, int32_t W) { return PoolWs(nullptr, F, H, W).bytes; }
 
 int nof_make_frame_rays(const nof_ray_pool_desc *desc, void *stream) {
     if (!desc) return set_error(NOF_EINVAL, "make_frame_rays: NULL desc");
@@ -380,27 +403,19 @@ int nof_make_frame_rays(const nof_ray_pool_desc *desc, void *stream) {
                          d.grid_dims[2] <= 0))
         return set_error(NOF_EINVAL, "make_frame_rays: bad denoise point grid");
     hipStream_t s = (hipStream_t)stream;
-    const size_t P = (size_t)d.F * d.H * d.W;
-    const int64_t nblk = (int64_t)((P + POOL_BLOCK - 1) / POOL_BLOCK);
-    char *ws = (char *)d.workspace;
-    uint8_t *hrow = (uint8_t *)ws;
-    uint8_t *dil = hrow + align256(P);
-    uint8_t *flag = dil + align256(P);
-    float *nearfar = (float *)(flag + align256(P));
-    int32_t *blk_count = (int32_t *)((char *)nearfar + align256(P * 8));
-    int64_t *blk_off = (int64_t *)((char *)blk_count + align256(nblk * 4));
-    hipLaunchKernelGGL(k_dilate_rows, dim3(d.H, d.F), dim3(POOL_BLOCK), 0, s, d, hrow);
-    hipLaunchKernelGGL(k_dilate_cols, dim3((d.W + 63) / 64, d.F), dim3(POOL_BLOCK), 0, s, d, hrow, dil);
-    hipLaunchKernelGGL(k_select, dim3((unsigned)nblk), dim3(POOL_BLOCK), 0, s, d, dil, flag, nearfar, blk_count);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, blk_count, nblk, blk_off);
-    hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk), dim3(POOL_BLOCK), 0, s, d, flag, nearfar, blk_off, nblk, d.rays,
-                       d.n_out);
+    const PoolWs ws(d.workspace, d.F, d.H, d.W);
+    const int64_t nblk = (int64_t)ws.nblk;
+    hipLaunchKernelGGL(k_dilate_rows, dim3(d.H, d.F), dim3(POOL_BLOCK), 0, s, d, ws.hrow);
+    hipLaunchKernelGGL(k_dilate_cols, dim3((d.W + 63) / 64, d.F), dim3(POOL_BLOCK), 0, s, d, ws.hrow, ws.dil);
+    hipLaunchKernelGGL(k_select, dim3((unsigned)nblk), dim3(POOL_BLOCK), 0, s, d, ws.dil, ws.flag, ws.nearfar,
+                       ws.blk_count);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, ws.blk_count, nblk, ws.blk_off);
+    hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk), dim3(POOL_BLOCK), 0, s, d, ws.flag, ws.nearfar, ws.blk_off, nblk,
+                       d.rays, d.n_out);
     return check_launch("make_frame_rays");
 }
 
-size_t nof_point_grid_workspace_bytes(int64_t n_cells) {
-    return align256((size_t)n_cells * 4) * 2 + align256((size_t)(n_cells + 1) * 8);
-}
+size_t nof_point_grid_workspace_bytes(int64_t n_cells) { return GridWs(nullptr, n_cells).bytes; }
 
 int nof_point_grid_build(const double *points, int32_t M, const double *origin, const int32_t *dims, double cell,
                          int32_t *cell_start, double *cell_points, int32_t *cell_ids, void *workspace, void *stream) {
@@ -416,15 +431,14 @@ int nof_point_grid_build(const double *points, int32_t M, const double *origin, 
         g.dims[a] = dims[a];
     }
     g.cell = cell;
-    int32_t *count = (int32_t *)workspace;
-    int32_t *cursor = (int32_t *)((char *)workspace + align256((size_t)nc * 4));
-    int64_t *start = (int64_t *)((char *)cursor + align256((size_t)nc * 4));
-    if (hipMemsetAsync(count, 0, (size_t)nc * 4, s) != hipSuccess || hipMemsetAsync(cursor, 0, (size_t)nc * 4, s) != hipSuccess)
+    const GridWs ws(workspace, nc);
+    if (hipMemsetAsync(ws.count, 0, (size_t)nc * 4, s) != hipSuccess ||
+        hipMemsetAsync(ws.cursor, 0, (size_t)nc * 4, s) != hipSuccess)
         return set_error(NOF_ELAUNCH, "point_grid_build: memset failed");
-    if (M > 0) hipLaunchKernelGGL(k_grid_count, dim3(div_up(M, 256)), dim3(256), 0, s, points, M, g, count);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, count, nc, start);
+    if (M > 0) hipLaunchKernelGGL(k_grid_count, dim3(div_up(M, 256)), dim3(256), 0, s, points, M, g, ws.count);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, ws.count, nc, ws.start);
     const unsigned nb = div_up((uint64_t)(M > nc + 1 ? M : nc + 1), 256);
-    hipLaunchKernelGGL(k_grid_fill, dim3(nb < 65535u ? nb : 65535u), dim3(256), 0, s, points, M, g, start, cursor,
+    hipLaunchKernelGGL(k_grid_fill, dim3(nb < 65535u ? nb : 65535u), dim3(256), 0, s, points, M, g, ws.start, ws.cursor,
                        cell_start, nc, cell_points, cell_ids);
     return check_launch("point_grid_build");
 }

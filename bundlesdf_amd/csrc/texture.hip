@@ -29,6 +29,7 @@
 //                  candidate within `radius` (see the kernel), its colour
 //                  added to the vertex's f64 sum and 1 to its count.
 #include "raster.h"
+#include "host_entry.h"
 
 #pragma clang fp contract(off)
 
@@ -301,12 +302,10 @@ int nof_vertex_color_accumulate(const uint64_t *zbuf, int32_t H, int32_t W, cons
         return set_error(NOF_EINVAL, "%s: n_vertices=%lld must be in [0, 2^31)", fn, (long long)n_vertices);
     if (!std::isfinite(radius) || radius <= 0) return set_error(NOF_EINVAL, "%s: radius=%g must be finite and > 0", fn, radius);
     if (!(min_depth > 0)) return set_error(NOF_EINVAL, "%s: min_depth=%g must be > 0", fn, (double)min_depth);
-    const struct { const void *p; const char *name; bool need; } ptrs[] = {
-        {zbuf, "zbuf", true}, {mask, "mask", true}, {colors, "colors", true}, {cam_in_ob, "cam_in_ob", true},
-        {ob_in_cam, "ob_in_cam", true}, {K, "K", true}, {V, "V", n_vertices > 0},
-        {color_sum, "color_sum", n_vertices > 0}, {count, "count", n_vertices > 0}};
-    for (const auto &a : ptrs)
-        if (a.need && !a.p) return set_error(NOF_EINVAL, "%s: %s is NULL", fn, a.name);
+    if (int rc = require_pointers(fn, {{zbuf, "zbuf"}, {mask, "mask"}, {colors, "colors"}, {cam_in_ob, "cam_in_ob"},
+                                       {ob_in_cam, "ob_in_cam"}, {K, "K"}, {V, "V", n_vertices > 0},
+                                       {color_sum, "color_sum", n_vertices > 0}, {count, "count", n_vertices > 0}}))
+        return rc;
     if (n_vertices == 0) return 0;
     hipLaunchKernelGGL(k_vertex_color, dim3(div_up(n_vertices, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned long long *)zbuf, H, W, mask, min_depth, colors, make_cam(cam_in_ob, K),
