@@ -266,13 +266,6 @@ def test_entry_points_refuse_bad_descriptors_before_device_work():
     assert lib.nof_fine_expectation(ctypes.byref(edesc(M=0, win_a=p, win_b=p, expec=p)), None) == 0
 
 
-@pytest.mark.parametrize("cname,pyname", [("nof_fine_windows_desc", "FineWindowsDesc"),
-                                          ("nof_fine_expectation_desc", "FineExpectationDesc")])
-def test_descriptor_mirrors_have_the_header_layout(tmp_path, cname, pyname):
-    from tests.test_lib_exports import test_descriptor_layout_matches_header as check
-    check(tmp_path, cname, pyname)
-
-
 def test_forward_inplace_rejects_what_it_cannot_update_in_place():
     from bundlesdf_amd import transformer as T
     ft = T.FeatureTransformer(O.TO.make_weights(3, 128, ("self",)), d_model=128, layer_names=("self",))

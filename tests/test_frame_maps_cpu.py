@@ -1,16 +1,12 @@
 """CPU: the frame-map oracle (tests/frame_maps_oracle.py) on its own scene, and the validation of
 bundlesdf_amd.frames, which raises before any device work."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import frame_maps_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_plane_normals_are_exact():
@@ -133,27 +129,3 @@ def test_library_refuses_bad_descriptors_before_device_work():
         assert fn(ctypes.byref(D), None) != 0
         assert word in L.nof_last_error(), (word, L.nof_last_error())
     assert L.nof_frame_erode(None, None) != 0 and b"desc is NULL" in L.nof_last_error()
-
-
-@pytest.mark.parametrize("cname,pyname", [("nof_frame_erode_desc", "FrameErodeDesc"),
-                                          ("nof_frame_bilateral_desc", "FrameBilateralDesc"),
-                                          ("nof_frame_geometry_desc", "FrameGeometryDesc"),
-                                          ("nof_frame_lift_desc", "FrameLiftDesc"),
-                                          ("nof_frame_covis_desc", "FrameCovisDesc")])
-def test_group10_descriptor_layout_matches_header(tmp_path, cname, pyname):
-    """The ctypes mirrors have the C header's field offsets and size (as test_lib_exports checks the older ones)."""
-    from bundlesdf_amd import _lib
-    S = getattr(_lib, pyname)
-    fields = [f[0] for f in S._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "nof.h")}"',
-           'int main(void) {', f'  printf("%zu\\n", sizeof({cname}));']
-    src += [f'  printf("%zu\\n", offsetof({cname}, {f.rstrip("_")}));' for f in fields]
-    src += ['  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(c)], check=True)
-    vals = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(S)
-    for f, off in zip(fields, vals[1:]):
-        assert getattr(S, f).offset == off, f

@@ -5,7 +5,6 @@ CoarseMatches.to_pixels; and the argument validation of match_descriptors and no
 which all happens before the first device call."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +13,6 @@ import torch
 from bundlesdf_amd import _lib
 from bundlesdf_amd import matching as M
 from tests import match_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _materialised(a, b, hw_a, hw_b, va=None, vb=None, temperature=0.1, thr=0.2, border_rm=2):
@@ -223,20 +220,3 @@ def test_workspace_does_not_grow_with_L_times_S():
     assert 0 < n <= 45 * (4 * 2500 + 3 * 2500) * 4 + 7 * 256
     assert n < 45 * 2500 * 2500 * 4 // 100
     assert L.nof_match_workspace_bytes(0, 5, 5) == 0
-
-
-def test_descriptor_layout_matches_header(tmp_path):
-    """MatchDesc has the C header's field offsets and size (gcc compiles include/nof.h)."""
-    fields = [f[0] for f in _lib.MatchDesc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "nof.h")}"',
-           'int main(void) {', '  printf("%zu\\n", sizeof(nof_match_desc));']
-    src += [f'  printf("%zu\\n", offsetof(nof_match_desc, {f}));' for f in fields]
-    src += ['  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(c)], check=True)
-    vals = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(_lib.MatchDesc)
-    for f, off in zip(fields, vals[1:]):
-        assert getattr(_lib.MatchDesc, f).offset == off, f

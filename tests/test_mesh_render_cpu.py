@@ -3,7 +3,6 @@ the C ABI's exports and refusals (validated before any HIP call, so they run wit
 Mesh.export -> Mesh.load round trips, and evaluate.mesh_frame_agreement on hand-made frames."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -102,26 +101,6 @@ def test_symbols_exported_and_bound(libnof):
     for name in ("nof_render_mesh", "nof_render_mesh_workspace_bytes"):
         assert name + "(" in header and name in _lib.declared_symbols() and hasattr(libnof, name)
     assert libnof.nof_render_mesh_workspace_bytes(2, 10, 4, 8) >= (2 * 4 * 8 + 2 * 10) * 8
-
-
-def test_descriptor_layout_matches_header(tmp_path):
-    from bundlesdf_amd import _lib
-    S = _lib.MeshRenderDesc
-    fields = [f[0] for f in S._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "nof.h")}"',
-           'int main(void) {', '  printf("%zu\\n", sizeof(nof_mesh_render_desc));']
-    src += [f'  printf("%zu\\n", offsetof(nof_mesh_render_desc, {f}));' for f in fields]
-    src += ['  printf("%d %d %d\\n", NOF_MESH_COLOUR_FLAT, NOF_MESH_COLOUR_VERTEX, NOF_MESH_COLOUR_TEXTURE);',
-            '  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(c)], check=True)
-    vals = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(S)
-    for f, off in zip(fields, vals[1:]):
-        assert getattr(S, f).offset == off, f
-    assert vals[-3:] == [_lib.MESH_COLOUR_FLAT, _lib.MESH_COLOUR_VERTEX, _lib.MESH_COLOUR_TEXTURE]
 
 
 def _valid_desc(buf, K):

@@ -2,8 +2,6 @@
 poses, the tie guard of the dense cases, and what the library and optimize_poses refuse before any
 device work. No GPU is needed."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,8 +9,6 @@ import pytest
 from bundlesdf_amd import _lib
 from bundlesdf_amd import pose_graph as PG
 from tests import pose_graph_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # weight 1e4 on two cases: at weight 1 the absolute 1e-6 guards of the PCG end the steps after the second
 DENSE_CASES = {
@@ -220,22 +216,3 @@ def test_library_refuses_bad_descriptors_before_device_work():
     refused(desc(workspace_bytes=16), b"workspace_bytes=16")
     assert L.nof_pose_graph_workspace_bytes(129, 0, 0, 0, 0) == 0
     assert L.nof_pose_graph_workspace_bytes(4, 2, 10, 24, 32) >= 4 * 128 + 24 * 24 * 8
-
-
-def test_descriptor_layout_matches_header(tmp_path):
-    """The ctypes mirror of nof_pose_graph_desc has the header's offsets and size (gcc compiles
-    include/nof.h and prints offsetof of every field)."""
-    S = _lib.PoseGraphDesc
-    fields = [f[0] for f in S._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "nof.h")}"',
-           'int main(void) {', '  printf("%zu\\n", sizeof(nof_pose_graph_desc));']
-    src += [f'  printf("%zu\\n", offsetof(nof_pose_graph_desc, {f}));' for f in fields]
-    src += ['  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(c)], check=True)
-    vals = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(S)
-    for f, off in zip(fields, vals[1:]):
-        assert getattr(S, f).offset == off, f

@@ -2,15 +2,11 @@
 validation (before any device work), the render oracle's depth rule on hand-made rows, and the
 schedule of NerfRunner.train()'s periodic outputs with a stub trainer."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import render_oracle as RO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -19,24 +15,6 @@ def libnof():
     build.build()
     from bundlesdf_amd import _lib
     return _lib.lib()
-
-
-def test_render_out_layout_matches_header(tmp_path):
-    """The method of test_descriptor_layout_matches_header: gcc prints the header's offsets and size."""
-    from bundlesdf_amd import _lib
-    fields = [f[0] for f in _lib.RenderOut._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "nof.h")}"',
-           'int main(void) {', '  printf("%zu\\n", sizeof(nof_render_out));']
-    src += [f'  printf("%zu\\n", offsetof(nof_render_out, {f}));' for f in fields]
-    src += ['  return 0;', '}']
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(c)], check=True)
-    vals = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(_lib.RenderOut) and len(vals) == len(fields) + 1
-    for f, off in zip(fields, vals[1:]):
-        assert getattr(_lib.RenderOut, f).offset == off, f
 
 
 def test_render_rays_refuses_bad_arguments_before_device_work(libnof):
