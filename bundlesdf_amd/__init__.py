@@ -13,16 +13,18 @@ reference's operator/module interfaces:
   bundlesdf_amd.matching      <- BundleTrack/LoFTR/src/loftr/utils/coarse_matching.py (match_descriptors)
   bundlesdf_amd.transformer   <- BundleTrack/LoFTR/src/loftr/loftr_module/transformer.py, utils/position_encoding.py
   bundlesdf_amd.fine          <- BundleTrack/LoFTR/src/loftr/loftr_module/fine_preprocess.py, utils/fine_matching.py
+  bundlesdf_amd.backbone      <- BundleTrack/LoFTR/src/loftr/backbone/resnet_fpn.py (ResNetFPN_8_2)
+  bundlesdf_amd.loftr         <- BundleTrack/LoFTR/src/loftr/loftr.py (LoFTR.forward)
 """
 __version__ = "0.1.0"
 
-__all__ = ["matching", "transformer", "fine"]
+__all__ = ["matching", "transformer", "fine", "backbone", "loftr"]
 
 
 def __getattr__(name):
-    # bundlesdf_amd.matching / .transformer / .fine without an import of their own; loaded on first use so
+    # bundlesdf_amd.matching / .transformer / ... without an import of their own; loaded on first use so
     # that `python -m bundlesdf_amd.build` does not pay for torch
-    if name in ("matching", "transformer", "fine"):
+    if name in __all__:
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

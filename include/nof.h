@@ -1213,6 +1213,41 @@ typedef struct {
 /* One launch on `stream` (k_fine_expect); validated as above, M == 0 returns NOF_OK with no launch. */
 int nof_fine_expectation(const nof_fine_expectation_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 14
+ * LoFTR backbone: the reference's ResNetFPN_8_2 (BundleTrack/LoFTR/src/loftr/backbone/
+ * resnet_fpn.py) in eval mode, initial_dim 128, block_dims [128, 196, 256]: a 7x7
+ * stride-2 stem, three stages of two residual blocks at 1/2, 1/4 and 1/8 of the image,
+ * and the FPN head. From N grey images (grey / 255) it gives the coarse tokens group 12
+ * takes and the fine map group 13 takes. Every convolution is an implicit GEMM on
+ * v_mfma_f32_32x32x16_f16 with fp16 operands (BatchNorm folded into the weights on the
+ * host) and f32 accumulation; the bias, the residual, the bilinear upsample and the
+ * activation are f32 and each activation is rounded once to fp16. Every sum runs in a
+ * fixed order and no floating-point atomic is used: the same bytes on every run and for
+ * every split of the images into calls. csrc/backbone.hip's header comment is the full
+ * definition, with the layout of `weights` (bundlesdf_amd/backbone.py packs it). */
+typedef struct {
+    const float *images;                  /* device [N,H,W] f32 */
+    int32_t N;                            /* >= 1 */
+    int32_t H, W;                         /* multiples of 8, 8 .. 4096 */
+    int32_t reserved;
+    const void *weights;                  /* device, laid out as csrc/backbone.hip states */
+    size_t weights_bytes;                 /* at least nof_backbone_weights_bytes() */
+    const float *pe;                      /* device [H/8 W/8,256] f32 added to coarse, or NULL */
+    float *coarse;                        /* device [N,H/8 W/8,256] f32 */
+    void *fine;                           /* device [N,H/2,W/2,128] fp16, channels last */
+    void *scratch;                        /* device */
+    size_t scratch_bytes;                 /* at least nof_backbone_scratch_bytes(N, H, W) */
+} nof_backbone_desc;
+
+/* The activations of a call; 0 for shapes that are refused. */
+size_t nof_backbone_scratch_bytes(int32_t N, int32_t H, int32_t W);
+size_t nof_backbone_weights_bytes(void);
+
+/* Twenty launches on `stream`; nothing is allocated or read back. images, weights, pe, coarse, fine and
+ * scratch are 16-byte aligned. The whole descriptor is validated before the first HIP call: NOF_EINVAL
+ * with nof_last_error naming the field. */
+int nof_backbone(const nof_backbone_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
