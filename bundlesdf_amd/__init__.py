@@ -15,10 +15,11 @@ reference's operator/module interfaces:
   bundlesdf_amd.fine          <- BundleTrack/LoFTR/src/loftr/loftr_module/fine_preprocess.py, utils/fine_matching.py
   bundlesdf_amd.backbone      <- BundleTrack/LoFTR/src/loftr/backbone/resnet_fpn.py (ResNetFPN_8_2)
   bundlesdf_amd.loftr         <- BundleTrack/LoFTR/src/loftr/loftr.py (LoFTR.forward)
+  bundlesdf_amd.pairs         <- BundleTrack/src/FeatureManager.cpp (processImagePair), Frame::updateRoi, find_corres
 """
 __version__ = "0.1.0"
 
-__all__ = ["matching", "transformer", "fine", "backbone", "loftr"]
+__all__ = ["matching", "transformer", "fine", "backbone", "loftr", "pairs"]
 
 
 def __getattr__(name):

@@ -16,6 +16,7 @@ shapes are the reference's (grid.py / nerf_helpers.py).
 """
 import ctypes
 import dataclasses
+import gc
 import math
 import os
 
@@ -687,10 +688,19 @@ class FusedStep:
             if kind == "graph":
                 g = torch.cuda.CUDAGraph()
                 self._capturing = True
+                # A dead reference cycle may hold an older CUDAGraph (a FusedStep dropped after a capture). If the
+                # cyclic collector frees it while this stream is capturing, its hipGraphDestroy is refused ("operation
+                # not permitted when stream is capturing") and the process aborts in the destructor. torch.cuda.graph
+                # no longer collects on entry, so collect here and keep the collector off until the capture has ended.
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
                 try:
                     with torch.cuda.graph(g):
                         self._graph_body(what, rays_per_frame, sched, R, t_rand)
                 finally:
+                    if gc_was_on:
+                        gc.enable()
                     self._capturing = False
                 plan.append(("graph", g))
             else:

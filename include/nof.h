@@ -1248,6 +1248,57 @@ size_t nof_backbone_weights_bytes(void);
  * with nof_last_error naming the field. */
 int nof_backbone(const nof_backbone_desc *d, void *stream);
 
+/* ------------------------------------------------------------------ group 15
+ * Pair crops: what the matcher is shown instead of whole frames (the reference's
+ * Frame::updateRoi, BundleTrack/src/Frame.cpp, and the cv::warpPerspective calls of
+ * processImagePair, BundleTrack/src/FeatureManager.cpp, over images zeroed outside the
+ * mask). The per-pair transforms are formed on the host (bundlesdf_amd/pairs.py); the
+ * warp takes their inverses. Pixel (u, v) = (column, row), images row-major. The
+ * definition of both calls, with the order of every operation, is the header comment of
+ * bundlesdf_amd/csrc/pair_crop.hip: IEEE f64 without contraction, outputs rounded once
+ * to float32, integer atomics only, the same bytes on every run. Every call launches on
+ * `stream`, allocates nothing, reads nothing back, and validates its whole descriptor
+ * before the first HIP call: NOF_EINVAL with nof_last_error naming the field.
+ */
+
+/* roi[f] = (umin, umax, vmin, vmax), inclusive, over the pixels of frame f with mask > 0,
+ * count[f] = their number; an empty mask gives (W, -1, H, -1) and 0. Both outputs are
+ * initialised by the call. N is 0 .. 65535 (0 returns NOF_OK with no launch), H and W at
+ * least 1, N H W < 2^31. */
+typedef struct {
+    const uint8_t *masks;                 /* device [N,H,W] u8 */
+    int32_t N, H, W;
+    int32_t reserved;
+    int32_t *roi;                         /* device [N,4] i32 */
+    int32_t *count;                       /* device [N] i32 */
+} nof_mask_roi_desc;
+int nof_mask_roi(const nof_mask_roi_desc *d, void *stream);
+
+/* the element type and layout of nof_warp_images_desc.images */
+#define NOF_WARP_GREY_U8 0                /* [N,H,W] u8, value / 255 */
+#define NOF_WARP_GREY_F32 1               /* [N,H,W] f32, already in 0..1 */
+#define NOF_WARP_RGB_U8 2                 /* [N,H,W,3] u8, (0.2989 R + 0.587 G) + 0.114 B per tap, / 255 */
+
+/* Q square crops of side S, bilinear in f64: crop q reads frame frames[q] through inv[q],
+ * the affine map from crop pixel (x, y) to source pixel. A tap outside the image, or
+ * where masks is 0, reads 0. A crop whose frames[q] lies outside 0 .. N-1 is written as
+ * zeros (cells too) and nothing is read for it. cells, when given, is 1 for each 8 x 8
+ * cell of a crop with a pixel whose nearest source pixel lies inside the image and the
+ * mask. S is a multiple of 8 in 8 .. 4096; Q >= 0 with Q ceil(S/32) < 2^31 (0 returns
+ * NOF_OK with no launch); N is 1 .. 65535, N H W < 2^31. */
+typedef struct {
+    const void *images;                   /* device, as `format` says */
+    const uint8_t *masks;                 /* device [N,H,W] u8 or NULL (no mask) */
+    int32_t N, H, W;
+    int32_t format;                       /* NOF_WARP_* */
+    const int32_t *frames;                /* device [Q] i32 */
+    const double *inv;                    /* device [Q,2,3] f64, row-major */
+    int32_t Q, S;
+    float *out;                           /* device [Q,S,S] f32 */
+    uint8_t *cells;                       /* device [Q,S/8,S/8] u8 or NULL (not formed) */
+} nof_warp_images_desc;
+int nof_warp_images(const nof_warp_images_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
