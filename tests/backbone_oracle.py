@@ -139,64 +139,275 @@ def fold(w, conv_name, bn_name):
     return _f16(W * s[:, None, None, None]), (b - m * s).astype(np.float32).astype(np.float64)
 
 
+def _up2_coords(h, ft):
+    y = np.arange(2 * h)
+    s = (y * (h - 1)).astype(ft) / ft(2 * h - 1)
+    y0 = np.floor(s).astype(np.int64)
+    return y0, np.minimum(y0 + 1, h - 1), (s - y0.astype(ft)).astype(ft)
+
+
+def _up2(x, coord_t, blend_t):
+    _, h, w, _ = x.shape
+    y0, y1, fy = _up2_coords(h, coord_t)
+    x0, x1, fx = _up2_coords(w, coord_t)
+    x = x.astype(blend_t)
+    fy, fx = fy.astype(blend_t)[None, :, None, None], fx.astype(blend_t)[None, None, :, None]
+    top = (1 - fx) * x[:, y0][:, :, x0] + fx * x[:, y0][:, :, x1]
+    bot = (1 - fx) * x[:, y1][:, :, x0] + fx * x[:, y1][:, :, x1]
+    return (1 - fy) * top + fy * bot
+
+
 def up2(x, rounded):
     """x [N,h,w,C] -> [N,2h,2w,C], bilinear, align_corners=True, in the order the definition states."""
     ft = np.float32 if rounded else np.float64
-
-    def coords(h):
-        y = np.arange(2 * h)
-        s = (y * (h - 1)).astype(ft) / ft(2 * h - 1)
-        y0 = np.floor(s).astype(np.int64)
-        return y0, np.minimum(y0 + 1, h - 1), (s - y0.astype(ft)).astype(ft)
-
-    _, h, w, _ = x.shape
-    y0, y1, fy = coords(h)
-    x0, x1, fx = coords(w)
-    x = x.astype(ft)
-    fy, fx = fy[None, :, None, None], fx[None, None, :, None]
-    top = (1 - fx) * x[:, y0][:, :, x0] + fx * x[:, y0][:, :, x1]
-    bot = (1 - fx) * x[:, y1][:, :, x0] + fx * x[:, y1][:, :, x1]
-    return ((1 - fy) * top + fy * bot).astype(np.float64)
+    return _up2(x, ft, ft).astype(np.float64)
 
 
-def forward(w, images, rounded=False):
-    """images [N,H,W] -> (coarse [N,256,H/8,W/8], fine [N,128,H/2,W/2]) float64, the module's layout."""
-    r = _f16 if rounded else (lambda v: v)
+# the 20 convolutions in the order of the device's BB_LAYERS, and the names forward() traces under
+LAYER_NAMES = tuple(n for n in conv_shapes() if "downsample" not in n)
+TRACE_KEYS = LAYER_NAMES + ("coarse",)
+
+
+def forward(w, images, rounded=False, trace=None):
+    """images [N,H,W] -> (coarse [N,256,H/8,W/8], fine [N,128,H/2,W/2]) float64, the module's layout.
+
+    trace, a dict, receives every stored activation as channels-last float64 [N,h,w,C]: the outputs of the
+    20 layers under LAYER_NAMES (layer3_outconv's is the fp16 copy when rounded) and x3_out as "coarse".
+
+    rounded=True keeps the accumulator in float64 and runs the epilogue as the device does, in float32: the
+    accumulator rounded to float32, + b', + the residual, + the upsampled term, relu or 0.01f * s, then one
+    rounding to fp16."""
+    f32 = np.float32
+
+    def keep(name, v):
+        if trace is not None:
+            trace[name] = v
+        return v
+
+    def epilogue(name, acc, b, res=None, up=None, act=None):
+        """acc f64 and b' -> the stored activation of layer `name`."""
+        if rounded:
+            v = acc.astype(f32) + b.astype(f32)
+            if res is not None:
+                v = v + res.astype(f32)
+            if up is not None:
+                v = v + up.astype(f32)
+            lr = f32(LRELU) * v
+        else:
+            v = acc + b + (0.0 if res is None else res) + (0.0 if up is None else up)
+            lr = LRELU * v
+        if act == "relu":
+            v = np.maximum(v, 0)
+        if act == "lrelu":
+            v = np.where(v > 0, v, lr)
+        return keep(name, _f16(v) if rounded else v.astype(np.float64))
 
     def cb(x, conv_name, bn_name, stride=1):
+        """(accumulator, bias): the folded convolution when rounded, else convolution then BatchNorm."""
         if rounded:
             W, b = fold(w, conv_name, bn_name)
-            return conv(x, W, stride) + b
+            return conv(x, W, stride), b
         y = conv(x, w[conv_name + ".weight"], stride)
         if bn_name is None:
-            return y
+            return y, 0.0
         g, b, m, v = (w[f"{bn_name}.{k}"].astype(np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
-        return (y - m) / np.sqrt(v + EPS) * g + b
+        return (y - m) / np.sqrt(v + EPS) * g + b, 0.0
 
     def block(x, p, stride):
-        y = r(np.maximum(cb(x, p + ".conv1", p + ".bn1", stride), 0.0))
+        y = epilogue(p + ".conv1", *cb(x, p + ".conv1", p + ".bn1", stride), act="relu")
+        a2, b2 = cb(y, p + ".conv2", p + ".bn2")
         if stride == 1:
-            return r(np.maximum(cb(y, p + ".conv2", p + ".bn2") + x, 0.0))
-        if not rounded:
-            return np.maximum(cb(y, p + ".conv2", p + ".bn2") + cb(x, p + ".downsample.0", p + ".downsample.1", 2), 0.0)
+            return epilogue(p + ".conv2", a2, b2, res=x, act="relu")
         # one accumulator for both products, the two biases summed in float32 first
-        (W2, b2), (Wd, bd) = fold(w, p + ".conv2", p + ".bn2"), fold(w, p + ".downsample.0", p + ".downsample.1")
-        bias = (b2.astype(np.float32) + bd.astype(np.float32)).astype(np.float64)
-        return r(np.maximum(conv(y, W2, 1) + conv(x, Wd, 2) + bias, 0.0))
+        ad, bd = cb(x, p + ".downsample.0", p + ".downsample.1", 2)
+        bias = (f32(b2) + f32(bd)).astype(np.float64) if rounded else 0.0
+        return epilogue(p + ".conv2", a2 + ad, bias, act="relu")
 
-    def lrelu(v):
-        return np.where(v > 0, v, LRELU * v)
-
+    r = _f16 if rounded else (lambda v: v)
     x = r(np.asarray(images, np.float64))[..., None]
-    x0 = r(np.maximum(cb(x, "conv1", "bn1", 2), 0.0))
+    x0 = epilogue("conv1", *cb(x, "conv1", "bn1", 2), act="relu")
     x1 = block(block(x0, "layer1.0", 1), "layer1.1", 1)
     x2 = block(block(x1, "layer2.0", 2), "layer2.1", 1)
     x3 = block(block(x2, "layer3.0", 2), "layer3.1", 1)
-    x3_out = cb(x3, "layer3_outconv", None)
-    t = r(cb(x2, "layer2_outconv", None) + up2(r(x3_out), rounded))
-    t = r(lrelu(cb(t, "layer2_outconv2.0", "layer2_outconv2.1")))
-    x2_out = r(cb(t, "layer2_outconv2.3", None))
-    t = r(cb(x1, "layer1_outconv", None) + up2(x2_out, rounded))
-    t = r(lrelu(cb(t, "layer1_outconv2.0", "layer1_outconv2.1")))
-    x1_out = r(cb(t, "layer1_outconv2.3", None))
+    x3_out = keep("coarse", cb(x3, "layer3_outconv", None)[0])
+    x3_16 = keep("layer3_outconv", r(x3_out))
+    t = epilogue("layer2_outconv", *cb(x2, "layer2_outconv", None), up=up2(x3_16, rounded))
+    t = epilogue("layer2_outconv2.0", *cb(t, "layer2_outconv2.0", "layer2_outconv2.1"), act="lrelu")
+    x2_out = epilogue("layer2_outconv2.3", *cb(t, "layer2_outconv2.3", None))
+    t = epilogue("layer1_outconv", *cb(x1, "layer1_outconv", None), up=up2(x2_out, rounded))
+    t = epilogue("layer1_outconv2.0", *cb(t, "layer1_outconv2.0", "layer1_outconv2.1"), act="lrelu")
+    x1_out = epilogue("layer1_outconv2.3", *cb(t, "layer1_outconv2.3", None))
     return x3_out.transpose(0, 3, 1, 2), x1_out.transpose(0, 3, 1, 2)
+
+
+# ---- the scratch buffer as an observation window ----
+
+# BbScratch of csrc/backbone.hip: (name, level, the C_p the part is sized for, the C_p of the tensor it holds
+# when the call returns), in the order the buffer is carved. m1 is sized for the 256 channels of
+# layer2_outconv's output and ends with x2_out, 196 -> 224 channels, packed at its start.
+SCRATCH_PARTS = (("s0", 2, 128, 128), ("s1", 2, 224, 224), ("s2", 2, 224, 224), ("m0", 4, 224, 224), ("m1", 4, 256, 224),
+                 ("m2", 4, 256, 256), ("c0", 8, 256, 256), ("c1", 8, 256, 256), ("c2", 8, 256, 256))
+# what a part holds when the call returns, as a key of forward()'s trace
+SCRATCH_HOLDS = {"s0": "layer1.1.conv2", "s1": "layer1_outconv", "s2": "layer1_outconv2.0", "m0": "layer2.1.conv2",
+                 "m1": "layer2_outconv2.3", "m2": "layer2_outconv2.0", "c0": "layer3.1.conv2", "c1": "layer3_outconv",
+                 "c2": "layer3.0.conv2"}
+
+
+def scratch_offsets(N, H, W):
+    """name -> (byte offset, (N, h, w, C_p)), and the buffer's size: the parts in order, each rounded up to
+    256 bytes, as bundlesdf_amd.backbone.scratch_bytes counts them."""
+    out, at = {}, 0
+    for name, level, sized, cp in SCRATCH_PARTS:
+        pixels = N * (H // level) * (W // level)
+        out[name] = (at, (N, H // level, W // level, cp))
+        at += (2 * pixels * sized + 255) // 256 * 256
+    return out, at
+
+
+def scratch_views(scratch_uint8, N, H, W):
+    """The nine activations of a call on N images of H x W as fp16 views [N,h,w,C_p] of its scratch buffer,
+    a flat uint8 torch tensor or numpy array (which may be longer than the call needed)."""
+    offsets, total = scratch_offsets(N, H, W)
+    assert scratch_uint8.ndim == 1 and scratch_uint8.shape[0] >= total, (tuple(scratch_uint8.shape), total)
+    views = {}
+    for name, (at, shape) in offsets.items():
+        part = scratch_uint8[at:at + 2 * int(np.prod(shape))]
+        if isinstance(part, np.ndarray):
+            views[name] = part.view(np.float16).reshape(shape)
+        else:
+            import torch
+            views[name] = part.view(torch.float16).view(shape)
+    return views
+
+
+# ---- integer runs: every product, partial sum and stored activation exact ----
+
+# Integer BatchNorm biases, bias[c] = base - c % 3, base per BatchNorm below: minus the 0.9 quantile of the
+# pre-activation that this file's float64 forward gives on exact_images("ragged"), layer after layer, so
+# that relu keeps about a tenth of the entries and the largest activation of the trunk stays below 1000.
+# One channel in 32 (c % 32 == 5) has the bias 1 + c % 3 instead: it stays alive where a level is a single
+# pixel and a 3x3 sum has one tap, as on the 8 x 8 case.
+EXACT_BIAS = {"bn1": -8, "layer1.0.bn1": -5, "layer1.0.bn2": -6, "layer1.1.bn1": -8, "layer1.1.bn2": -9,
+              "layer2.0.bn1": -13, "layer2.0.bn2": -18, "layer2.0.downsample.1": 0, "layer2.1.bn1": -21,
+              "layer2.1.bn2": -33, "layer3.0.bn1": -38, "layer3.0.bn2": -71, "layer3.0.downsample.1": 0,
+              "layer3.1.bn1": -85, "layer3.1.bn2": -127, "layer2_outconv2.1": -50, "layer1_outconv2.1": -13}
+
+
+def exact_images(case):
+    """[N,H,W] float32 integers 0..7, drawn from the case's seed."""
+    c = CASES[case]
+    rng = np.random.default_rng(c["seed"] + 1000)
+    return rng.integers(0, 8, (c["N"], c["H"], c["W"])).astype(np.float32)
+
+
+def exact_weights(kind):
+    """Weights under which the device's arithmetic is exact. Every convolution is ternary: output channel o
+    has one +-1 per tap t, at input channel (5 o + 37 t + 11) % Cin with sign (-1)^(o + t + o // 9), so every
+    (tap, channel) column of a matrix with Cout >= Cin is hit (5 is coprime to 128, 196 and 256); the stem
+    keeps the taps t with (t + 6 o) % 49 < 8 of channel o. BatchNorm is weight 1, mean 0, var float32(1 -
+    1e-5): the float64 fold rounds to the same ternary W', and b' is the integer bias of EXACT_BIAS.
+    kind "head" is "trunk" with layer3_outconv and layer2_outconv2.3 zero: both up2 terms are then 0 and
+    layer2_outconv, layer2_outconv2.0, layer1_outconv and layer1_outconv2.0 are exact too."""
+    assert kind in ("trunk", "head"), kind
+    w = {}
+    for name, (cout, cin, k) in conv_shapes().items():
+        W = np.zeros((cout, cin, k, k), np.float32)
+        o = np.arange(cout)
+        for t in range(k * k):
+            sign = 1.0 - 2.0 * ((o + t + o // 9) % 2)
+            if cin == 1:
+                sign = sign * ((t + 6 * o) % 49 < 8)
+            W[o, (5 * o + 37 * t + 11) % cin, t // k, t % k] = sign
+        w[name + ".weight"] = W
+    for name, c in norm_shapes().items():
+        w[name + ".weight"] = np.ones(c, np.float32)
+        ch = np.arange(c)
+        w[name + ".bias"] = np.where(ch % 32 == 5, 1 + ch % 3, EXACT_BIAS[name] - ch % 3).astype(np.float32)
+        w[name + ".running_mean"] = np.zeros(c, np.float32)
+        w[name + ".running_var"] = np.full(c, 1.0 - EPS, np.float32)
+    if kind == "head":
+        for name in ("layer3_outconv", "layer2_outconv2.3"):
+            w[name + ".weight"] = np.zeros_like(w[name + ".weight"])
+    return w
+
+
+# ---- one layer from given inputs ----
+
+def layer_spec(li):
+    """(convolution, its BatchNorm or None, (skip convolution, its BatchNorm) or None, stride, activation) of
+    layer li of LAYER_NAMES."""
+    name = LAYER_NAMES[li]
+    bn = None
+    if li <= 12:
+        bn = name.replace("conv", "bn")                             # conv1 -> bn1, layerS.B.convC -> layerS.B.bnC
+    elif name.endswith("outconv2.0"):
+        bn = name[:-1] + "1"
+    skip = (name[:-5] + "downsample.0", name[:-5] + "downsample.1") if name in ("layer2.0.conv2", "layer3.0.conv2") else None
+    stride = 2 if name in ("conv1", "layer2.0.conv1", "layer3.0.conv1") else 1
+    act = "relu" if li <= 12 else "lrelu" if name.endswith("outconv2.0") else None
+    return name, bn, skip, stride, act
+
+
+# layer -> the layers whose outputs it reads as (input, skip, residual, up source); -1 is the image
+LAYER_INPUTS = {0: (-1, None, None, None), 1: (0, None, None, None), 2: (1, None, 0, None), 3: (2, None, None, None),
+                4: (3, None, 2, None), 5: (4, None, None, None), 6: (5, 4, None, None), 7: (6, None, None, None),
+                8: (7, None, 6, None), 9: (8, None, None, None), 10: (9, 8, None, None), 11: (10, None, None, None),
+                12: (11, None, 10, None), 13: (12, None, None, None), 14: (8, None, None, 13), 15: (14, None, None, None),
+                16: (15, None, None, None), 17: (4, None, None, 16), 18: (17, None, None, None), 19: (18, None, None, None)}
+
+
+def layer_inputs(li, trace, images):
+    """The keyword arguments of layer_reference for layer li from a trace of forward() on images."""
+    get = lambda i: None if i is None else np.asarray(images)[..., None] if i < 0 else trace[LAYER_NAMES[i]]
+    x, skip, res, up = LAYER_INPUTS[li]
+    return dict(x=get(x), skip=get(skip), res=get(res), up=get(up))
+
+
+def layer_columns(li):
+    """K of layer li: the column count of the matrix the device multiplies by, pad columns included."""
+    name, _, skip, _, _ = layer_spec(li)
+    pad = lambda c: (c + 31) // 32 * 32
+    shapes = conv_shapes()
+    _, cin, k = shapes[name]
+    return 64 if cin == 1 else k * k * pad(cin) + (pad(shapes[skip[0]][1]) if skip else 0)
+
+
+def layer_reference(w, li, x, skip=None, res=None, up=None):
+    """Layer li alone in float64 from fp16 inputs, channels-last with or without their pad channels: x the
+    input, skip the block input of a fused 1x1 stride-2 shortcut, res the residual, up the coarser map that
+    up2 reads -> (the value before the final rounding to fp16 [N,ho,wo,Cout], A), A = sum |W'||x| + |b'| +
+    |res| + the up2 blend of |up| per element: what the float32 rounding errors scale with. The up2
+    coordinates are the definition's float32 values; everything else is float64."""
+    name, bn, sk, stride, act = layer_spec(li)
+    assert (sk is None) == (skip is None), name
+    f64 = lambda v, c: np.asarray(v, np.float16).astype(np.float64)[..., :c]
+    cout, cin, _ = conv_shapes()[name]
+    W, b = fold(w, name, bn)
+    x = f64(x, cin)
+    v, A = conv(x, W, stride), conv(np.abs(x), np.abs(W), stride)
+    if sk is not None:
+        Wd, bd = fold(w, *sk)
+        s = f64(skip, Wd.shape[1])
+        v, A = v + conv(s, Wd, 2), A + conv(np.abs(s), np.abs(Wd), 2)
+        b = (b.astype(np.float32) + bd.astype(np.float32)).astype(np.float64)
+    v, A = v + b, A + np.abs(b)
+    if res is not None:
+        v, A = v + f64(res, cout), A + np.abs(f64(res, cout))
+    if up is not None:
+        u = f64(up, cout)
+        v, A = v + _up2(u, np.float32, np.float64), A + _up2(np.abs(u), np.float32, np.float64)
+    if act == "relu":
+        v = np.maximum(v, 0.0)
+    if act == "lrelu":
+        v = np.where(v > 0, v, float(np.float32(LRELU)) * v)
+    return v, A
+
+
+def layer_bound(li, got, ref, A, half=True):
+    """The isolation bound per element: half an fp16 ulp of the larger of got and ref (normal and
+    subnormal) when the value was stored as fp16, plus (K + 8) 2^-23 A for a float32 sum of K exact products
+    in any order and either MFMA rounding mode and the epilogue's few operations."""
+    ulp = 2.0 ** -11 * np.maximum(np.abs(got), np.abs(ref)) + 2.0 ** -24 if half else 0.0
+    return ulp + (layer_columns(li) + 8) * 2.0 ** -23 * A
+
+

@@ -97,6 +97,159 @@ def test_no_trace_of_the_pad_channels(net, cuda_device):
     assert tuple(dirty[0].shape) == (1, 3 * 9, 256) and tuple(dirty[1].shape) == (1, 12, 36, 128)
 
 
+# ---- exact integer runs and one-layer bounds (profiles/r25/backbone_layerwise.md) ----
+#
+# The parity bound above spans 20 layers and two networks that round at different points; a slip the size of
+# one fp16 rounding passes it. Below nothing is end to end: under tests/backbone_oracle.exact_weights every
+# product, partial sum and stored activation is an integer that fp16 and float32 hold exactly, so the
+# device must equal the float64 oracle with no tolerance; and the layers whose input and output both
+# survive in the scratch buffer are checked alone from the device's own input, to a bound derived from the
+# number formats (O.layer_bound).
+
+EXACT_CASES = ("ragged", "one_cell")
+ISOLATED = {13: ("c0", "c1"), 16: ("m2", "m1"), 17: ("s0", "s1"), 18: ("s1", "s2"), 19: ("s2", "fine")}   # layer -> (input, output)
+
+
+def _forward_snapshot(net, x, poison=False):
+    """One call -> (coarse [N,hc,wc,256] f32, fine f16, the nine scratch tensors), numpy copies taken before
+    anything else runs. poison: the scratch buffer holds 0xff bytes (fp16 NaN) when the call starts."""
+    N, H, W = x.shape
+    if poison:
+        if x.device not in net._scratch:
+            net.forward(x, position_encoding=False)
+        net._scratch[x.device].fill_(0xff)
+    coarse, fine, (hc, wc) = net.forward(x, position_encoding=False)
+    views = O.scratch_views(net._scratch[x.device], N, H, W)
+    snap = {k: v.cpu().numpy() for k, v in views.items()}
+    snap["coarse"] = coarse.cpu().numpy().reshape(N, hc, wc, 256)
+    snap["fine"] = fine.cpu().numpy()
+    return snap
+
+
+@pytest.fixture(scope="module")
+def exact_runs(cuda_device):
+    """(kind, case) -> (snapshot of the device's call on poisoned scratch, the oracle's trace), computed once."""
+    from bundlesdf_amd.backbone import Backbone
+    dev = torch.device(cuda_device)
+    dev = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    out = {"dev": dev}
+    for kind in ("trunk", "head"):
+        w = O.exact_weights(kind)
+        out[kind] = net = Backbone(w, device=dev)
+        for case in EXACT_CASES:
+            images = O.exact_images(case)
+            trace = {}
+            O.forward(w, images, rounded=True, trace=trace)
+            out[kind, case] = (_forward_snapshot(net, torch.from_numpy(images).to(dev), poison=True), trace)
+    return out
+
+
+def _assert_holds(snap, trace, part):
+    """The scratch part equals the oracle's activation in its real channels and is 0 in its pad channels."""
+    want = trace[O.SCRATCH_HOLDS[part]]
+    C = want.shape[-1]
+    got = snap[part].astype(np.float64)
+    np.testing.assert_array_equal(got[..., :C], want, err_msg=part)
+    np.testing.assert_array_equal(got[..., C:], 0.0, err_msg=part + " pad channels")   # NaN where nobody wrote
+
+
+@pytest.mark.parametrize("case", EXACT_CASES)
+def test_exact_trunk_equals_the_oracle_bit_for_bit(exact_runs, case):
+    """Stem, the six BasicBlocks (stride 2 and the fused skip included) and layer3_outconv, no tolerance."""
+    snap, trace = exact_runs["trunk", case]
+    for part in ("s0", "m0", "c0", "c2", "c1"):
+        _assert_holds(snap, trace, part)
+    assert snap["m0"].shape[-1] == 224 and trace[O.SCRATCH_HOLDS["m0"]].shape[-1] == 196      # 28 pad channels
+    assert snap["coarse"].dtype == np.float32
+    np.testing.assert_array_equal(snap["coarse"].astype(np.float64), trace["coarse"])
+
+    # N = 2 in one call and in two calls
+    net, dev = exact_runs["trunk"], exact_runs["dev"]
+    x = torch.from_numpy(O.exact_images(case)).to(dev)
+    x = x if x.shape[0] == 2 else torch.cat([x, x.flip(2)])
+    both = _forward_snapshot(net, x)
+    if case == "ragged":
+        for key in both:
+            np.testing.assert_array_equal(both[key], snap[key], err_msg=key)
+    for n in range(2):
+        one = _forward_snapshot(net, x[n:n + 1])
+        for key in ("s0", "m0", "c0", "c2", "c1", "coarse", "fine"):
+            np.testing.assert_array_equal(one[key], both[key][n:n + 1], err_msg=f"{key} image {n}")
+
+
+@pytest.mark.parametrize("case", EXACT_CASES)
+def test_exact_head_equals_the_oracle_bit_for_bit(exact_runs, case):
+    """layer3_outconv and layer2_outconv2.3 zero: both up2 terms are 0, and layer2_outconv (through
+    layer2_outconv2.0, whose input it is), layer2_outconv2.0, layer1_outconv and layer1_outconv2.0 are exact;
+    lrelu's negative branch is one float32 product rounded to fp16."""
+    snap, trace = exact_runs["head", case]
+    for part in ("m2", "s1", "s2", "s0", "m0", "c0"):
+        _assert_holds(snap, trace, part)
+    assert snap["s1"].shape[-1] == snap["s2"].shape[-1] == 224
+    for part in ("m1", "c1", "coarse"):
+        np.testing.assert_array_equal(snap[part], 0.0, err_msg=part)
+
+
+@pytest.fixture(scope="module")
+def isolated(net, cuda_device):
+    """case -> snapshot of the device's call with the random weights (the scratch buffer is shared between the
+    cases, so each is copied right after its call)."""
+    dev = torch.device(cuda_device)
+    dev = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    return {case: _forward_snapshot(net, torch.from_numpy(O.make_images(case)).to(dev)) for case in O.CASES}
+
+
+@pytest.fixture(scope="module")
+def random_weights():
+    return O.make_weights()
+
+
+@pytest.mark.parametrize("li", sorted(ISOLATED))
+@pytest.mark.parametrize("case", list(O.CASES))
+def test_one_layer_from_the_devices_own_input(isolated, random_weights, case, li):
+    """|got - ref| <= 2^-11 max(|got|, |ref|) + 2^-24 + (K + 8) 2^-23 A for every element: half an fp16 ulp
+    (normal, subnormal) for the one rounding of the store, and a float32 sum of K exact products in any order
+    with the epilogue's few operations, A = sum |w||x| + |b'| + |res| + |up taps|. Derived, not tuned."""
+    snap = isolated[case]
+    src, dst = ISOLATED[li]
+    ref, A = O.layer_reference(random_weights, li, snap[src], up=snap["m1"] if li == 17 else None)
+    C = ref.shape[-1]
+    got = snap[dst].astype(np.float64)
+    assert np.isfinite(got).all() and np.abs(ref).max() > 0.1
+    err = np.abs(got[..., :C] - ref)
+    ratio = err / O.layer_bound(li, got[..., :C], ref, A)
+    print(f"layer {li} {case}: max err {err.max():.3e}, max err / bound {ratio.max():.3f}")
+    assert (ratio <= 1.0).all(), (case, li, float(ratio.max()))
+    np.testing.assert_array_equal(got[..., C:], 0.0)
+    if li == 13:
+        coarse = snap["coarse"]
+        r32 = np.abs(coarse.astype(np.float64) - ref) / O.layer_bound(li, coarse, ref, A, half=False)
+        print(f"layer 13 {case} coarse: max err / bound {r32.max():.3f}")
+        assert (r32 <= 1.0).all(), (case, float(r32.max()))
+        np.testing.assert_array_equal(snap["c1"].view(np.uint16), coarse.astype(np.float16).view(np.uint16))
+
+
+def test_float32_images_are_rounded_to_fp16_to_nearest_even(net, cuda_device):
+    """The stem rounds the image when it stages it: a float32 image gives the bytes of that image rounded to
+    fp16 on the host. 1 + 2^-11 lies half-way between 1 and 1 + 2^-10 and goes down to the even 1;
+    1 + 3 2^-11 lies half-way between 1 + 2^-10 and 1 + 2^-9 and goes up to the even 1 + 2^-9."""
+    rng = np.random.default_rng(77)
+    x = rng.random((2, 16, 24)).astype(np.float32)
+    lo, hi = np.float32(1 + 2.0 ** -11), np.float32(1 + 3 * 2.0 ** -11)
+    x[:, ::3, ::5], x[:, 1::3, 2::5] = lo, hi
+    x16 = x.astype(np.float16)
+    assert float(np.float16(lo)) == 1.0 < lo and float(np.float16(hi)) == 1 + 2.0 ** -9 > hi
+    assert (x16.astype(np.float32) != x).mean() > 0.9
+    want = net.forward(torch.from_numpy(x16.astype(np.float32)).to(cuda_device), position_encoding=False)
+    got = net.forward(torch.from_numpy(x).to(cuda_device), position_encoding=False)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    # the two half-way values matter: rounding them the other way changes the output
+    other = x16.copy()
+    other[:, ::3, ::5], other[:, 1::3, 2::5] = np.float16(1 + 2.0 ** -10), np.float16(1 + 2.0 ** -10)
+    moved = net.forward(torch.from_numpy(other.astype(np.float32)).to(cuda_device), position_encoding=False)
+    assert not torch.equal(moved[1], want[1])
+
+
 def _scene_images(dev):
     """Two renders of the shared synthetic mesh at 96 x 128 -> (rgb uint8 [2,96,128,3], grey [2,96,128] f32)."""
     from bundlesdf_amd.compat.loftr_wrapper import to_grey
