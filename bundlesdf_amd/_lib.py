@@ -108,6 +108,6 @@ def require_device(t, name):
         raise RuntimeError(f"{name} must be a CUDA tensor")
 
 
-def require_contiguous(t, name):
+def require_contiguous(t, name, wording="a contiguous tensor"):
     if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be a contiguous tensor")
+        raise RuntimeError(f"{name} must be {wording}")

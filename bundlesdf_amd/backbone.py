@@ -18,7 +18,8 @@ import torch
 
 from . import _lib
 from . import transformer as _T
-from .transformer import _as_numpy, pack_matrix
+from ._args import PackedWeights, as_tensor, default_device
+from .transformer import pack_matrix
 
 __all__ = ["Backbone", "fold_batchnorm", "conv_matrix", "pack_conv", "pad_channels", "weight_layout", "scratch_bytes",
            "LAYERS", "BN_EPS", "C_COARSE", "C_FINE", "MAX_SIDE", "STEM_K"]
@@ -110,16 +111,7 @@ def scratch_bytes(N, H, W):
     return sum((p * c * 2 + 255) // 256 * 256 for p, c in parts)
 
 
-def _find_prefix(sd):
-    found = [k[:-len(_PROBE)] for k in sd if k.endswith(_PROBE)]
-    if len(found) == 1:
-        return found[0]
-    if not found:
-        raise ValueError(f"Backbone: key {_PROBE!r} is missing under every prefix")
-    raise ValueError(f"Backbone: prefixes {sorted(found)} all hold a backbone, name one")
-
-
-class Backbone:
+class Backbone(PackedWeights):
     """ResNetFPN_8_2 with its weights folded and packed for the device.
 
     weights maps the reference's parameter names (conv1.weight, bn1.{weight,bias,running_mean,running_var},
@@ -132,12 +124,7 @@ class Backbone:
         what = "Backbone"
 
         def get(key, shape):
-            if prefix + key not in weights:
-                raise ValueError(f"{what}: key {prefix + key!r} is missing")
-            v = _as_numpy(weights[prefix + key])
-            if tuple(v.shape) != shape:
-                raise ValueError(f"{what}: key {prefix + key!r} has shape {tuple(v.shape)}, expected {shape}")
-            return v
+            return self.lookup(weights, prefix, key, shape, what)
 
         def folded(conv, bn):
             Cout, Cin, KH = _SHAPES[conv]
@@ -156,29 +143,18 @@ class Backbone:
             bias = np.zeros(pad_channels(W.shape[0]), np.float32)
             bias[:W.shape[0]] = b
             parts += [pack_conv(W, Ws).view(np.uint8).ravel(), bias.view(np.uint8)]
-        self.packed = np.concatenate(parts)
+        super().__init__(np.concatenate(parts), device)
         assert self.packed.size == weight_layout()[1]
-        self._weights = {}          # device -> uint8 tensor
-        self._scratch = {}          # device -> uint8 tensor, grown on demand
+        self._scratch = self._buffers           # the name tests and scripts read
         self._pe = {}               # (device, hc, wc, temp_bug_fix) -> [hc wc, 256] f32
-        if device is not None:
-            self._device_weights(torch.device(device))
 
     @classmethod
     def from_state_dict(cls, sd, prefix=None, device=None):
         """From a checkpoint's state dict. prefix is what stands before 'conv1.weight' ('', 'backbone.',
         'matcher.backbone.'); None finds it."""
         if prefix is None:
-            prefix = _find_prefix(sd)
+            prefix = cls.find_prefix(sd, _PROBE, "Backbone", "a backbone")
         return cls(sd, device=device, prefix=prefix)
-
-    def _device_weights(self, dev):
-        dev = torch.device(dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._weights:
-            self._weights[dev] = torch.from_numpy(self.packed).to(dev)
-        return self._weights[dev]
 
     def forward(self, images, position_encoding=True, temp_bug_fix=False):
         """images [N,H,W] or [N,1,H,W] (array or tensor, any float dtype, grey / 255), H and W multiples of
@@ -187,7 +163,7 @@ class Backbone:
         (transformer.position_encoding) unless position_encoding is False: what FeatureTransformer.forward
         and FineRefiner.refine take."""
         what = "Backbone.forward"
-        t = images if torch.is_tensor(images) else torch.from_numpy(np.asarray(images))
+        t = as_tensor(images)
         if not t.is_floating_point():
             raise ValueError(f"{what}: images must be a floating-point array, got {t.dtype}")
         if t.dim() == 4 and t.shape[1] == 1:
@@ -200,16 +176,12 @@ class Backbone:
         if H < 8 or W < 8 or H % 8 or W % 8 or H > MAX_SIDE or W > MAX_SIDE:
             raise ValueError(f"{what}: the images are {H}x{W}: both sides must be multiples of 8 in 8..{MAX_SIDE}")
         hc, wc = H // 8, W // 8
-        dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        dev = default_device(t)
         lib = _lib.lib()
         with torch.cuda.device(dev):
-            x = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            w = self._device_weights(dev)
-            dev = w.device
-            nbytes = int(lib.nof_backbone_scratch_bytes(N, H, W))
-            ws = self._scratch.get(dev)
-            if ws is None or ws.numel() < nbytes:
-                ws = self._scratch[dev] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            x = t.to(device=dev, dtype=torch.float32).contiguous()
+            w = self.device_weights(dev)
+            ws = self.buffer(dev, int(lib.nof_backbone_scratch_bytes(N, H, W)))
             pe = None
             if position_encoding:
                 key = (dev, hc, wc, bool(temp_bug_fix))

@@ -30,17 +30,11 @@ def reset_sampler_errors(device=None):
     _err_counter(device).zero_()
 
 
-def _check_input(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be contiguous")
-
-
 def sampleRaysUniformOccupiedVoxels(z_in_out, z_sampled, z_vals):
     """common.cu:107-125: map stratified u in [0, sum(len)] to z through the ray's packed boxes."""
     for n, t in (("z_in_out", z_in_out), ("z_sampled", z_sampled), ("z_vals", z_vals)):
-        _check_input(t, n)
+        _lib.require_device(t, n)
+        _lib.require_contiguous(t, n, "contiguous")       # the reference's wording
     if z_vals.shape != z_sampled.shape:
         raise RuntimeError("z_vals.sizes()==z_sampled.sizes()")
     for n, t in (("z_in_out", z_in_out), ("z_sampled", z_sampled), ("z_vals", z_vals)):
@@ -58,9 +52,10 @@ def postprocessOctreeRayTracing(ray_index, depth_in_out, unique_intersect_ray_id
                                 N_rays):
     """common.cu:151-167. Returns [N_rays, max_intersections, 2] f32 on the *input's* device
     (the reference hard-codes cuda:0, common.cu:158)."""
-    for n, t in (("ray_index", ray_index), ("depth_in_out", depth_in_out), ("start_poss", start_poss)):
-        _check_input(t, n)
-    _check_input(unique_intersect_ray_ids, "unique_intersect_ray_ids")
+    for n, t in (("ray_index", ray_index), ("depth_in_out", depth_in_out), ("start_poss", start_poss),
+                 ("unique_intersect_ray_ids", unique_intersect_ray_ids)):
+        _lib.require_device(t, n)
+        _lib.require_contiguous(t, n, "contiguous")       # the reference's wording
     for n, t in (("ray_index", ray_index), ("unique_intersect_ray_ids", unique_intersect_ray_ids),
                  ("start_poss", start_poss)):
         if t.dtype != torch.int64:
@@ -80,7 +75,8 @@ def rayColorToTextureImageCUDA(F, V, hit_locations, hit_face_ids, uvs_tex, uvs):
     """common.cu:223-238: barycentric UV per hit, written into uvs [M,2]."""
     for n, t in (("F", F), ("V", V), ("hit_locations", hit_locations), ("hit_face_ids", hit_face_ids),
                  ("uvs_tex", uvs_tex), ("uvs", uvs)):
-        _check_input(t, n)
+        _lib.require_device(t, n)
+        _lib.require_contiguous(t, n, "contiguous")       # the reference's wording
     if F.dtype != torch.int64 or hit_face_ids.dtype != torch.int64:
         raise RuntimeError("F / hit_face_ids: expected scalar type Long")
     for n, t in (("V", V), ("hit_locations", hit_locations), ("uvs_tex", uvs_tex), ("uvs", uvs)):

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_host, as_tensor, default_device
 from .handoff import PointCloud
 from .mesh import trimesh_clean, trimesh_split
 
@@ -31,13 +32,8 @@ RIGID_TOL = 1e-6          # max |R R^T - I| of a pose add_err / adi_err accept
 _FRAME_CHUNK_POINTS = 1 << 22   # add_err: frames x model points transformed at a time
 
 
-def _dev(device=None):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def _points(a, device):
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
-    return t.to(device, torch.float64).reshape(-1, 3).contiguous()
+    return as_tensor(a, np.float64).to(device, torch.float64).reshape(-1, 3).contiguous()
 
 
 class PointGrid:
@@ -50,9 +46,7 @@ class PointGrid:
     The edge grows by a quarter at a time until the grid has at most 2^24 cells."""
 
     def __init__(self, points, cell=None, device=None):
-        if device is None and torch.is_tensor(points) and points.is_cuda:
-            device = points.device
-        self.device = _dev(device)
+        self.device = default_device(points, device)
         p = _points(points, self.device)
         n = len(p)
         if n == 0:
@@ -111,7 +105,7 @@ def nearest(queries, cloud_or_grid, transforms=None, max_dist=None):
     Q = len(q)
     T, single = None, True
     if transforms is not None:
-        T = transforms if torch.is_tensor(transforms) else torch.from_numpy(np.asarray(transforms, np.float64))
+        T = as_tensor(transforms, np.float64)
         single = T.dim() == 2
         T = T.to(dev, torch.float64).reshape(-1, 4, 4).contiguous()
     B = 1 if T is None else len(T)
@@ -155,7 +149,7 @@ def add_err(pred, gt, model_pts):
     under the predicted and the ground-truth pose. One 4x4 each -> float; [F,4,4] -> [F] f64 numpy.
     Poses must be rigid (ValueError otherwise)."""
     P, G, single = _poses(pred, gt, "add_err")
-    dev = _dev(model_pts.device if torch.is_tensor(model_pts) and model_pts.is_cuda else None)
+    dev = default_device(model_pts)
     m = _points(model_pts, dev)
     Pd, Gd = torch.from_numpy(P).to(dev), torch.from_numpy(G).to(dev)
     out = torch.empty(len(P), dtype=torch.float64, device=dev)
@@ -222,7 +216,7 @@ def sample_surface(mesh, count, seed=0, device=None):
     area, points uniform in the face (barycentric, the pair reflected when it falls outside). The draws
     come from a torch.Generator on the device seeded with `seed`: the same seed gives the same points,
     but trimesh's numpy stream cannot be reproduced here — only the distribution matches."""
-    dev = _dev(device)
+    dev = default_device(device=device)
     v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, np.float64)).to(dev)
     f = torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int64)).to(dev)
     if len(f) == 0:
@@ -345,7 +339,7 @@ def evaluate_mesh(pred_mesh, gt_pts, voxel=0.005, n_samples=99999, icp_thres=0.0
     result give the mutual chamfer distance to gt_pts, in cm. The input mesh is not modified."""
     if backend not in ("scipy", "hip"):
         raise ValueError(f"evaluate_mesh: backend must be 'scipy' or 'hip', got {backend!r}")
-    gt = np.asarray(gt_pts.cpu() if torch.is_tensor(gt_pts) else gt_pts, np.float64).reshape(-1, 3)
+    gt = as_host(gt_pts, np.float64).reshape(-1, 3)
     mesh = pred_mesh.copy()
     hi, lo = gt.max(0) + 0.3, gt.min(0) - 0.3
     mesh.update_vertices(~((mesh.vertices > hi).any(1) | (mesh.vertices < lo).any(1)))
@@ -382,9 +376,7 @@ def mesh_frame_agreement(render_depth, render_mask, obs_depth, obs_mask, max_dep
     the two middle values for an even count) of |rendered - observed| over the intersection, count
     is its size. A frame with an empty intersection reports iou 0 (also when the union is empty),
     count 0 and differences 0: no NaN."""
-    def t(a):
-        return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    rd, rm, od, om = t(render_depth), t(render_mask), t(obs_depth), t(obs_mask)
+    rd, rm, od, om = (as_tensor(a) for a in (render_depth, render_mask, obs_depth, obs_mask))
     dev = rd.device
     H, W = rd.shape[-2:]
     rd, od = rd.reshape(-1, H * W).double(), od.to(dev).reshape(-1, H * W).double()

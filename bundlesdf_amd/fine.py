@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .matching import CoarseMatches, _round_half_away
-from .transformer import MAX_PAIRS, FeatureTransformer, _as_numpy, pack_matrix
+from ._args import PackedWeights, as_tensor, cells_to_pixels, default_device
+from .matching import CoarseMatches
+from .transformer import MAX_PAIRS, FeatureTransformer, pack_matrix
 
 __all__ = ["FineRefiner", "FineMatches", "WINDOW", "C_FINE", "C_COARSE", "WEIGHT_BYTES", "MAX_SIDE"]
 
@@ -35,25 +36,6 @@ MAX_SIDE = 32768                                                # stride h, stri
 _KEYS = (("fine_preprocess.down_proj.weight", (C_FINE, C_COARSE)), ("fine_preprocess.down_proj.bias", (C_FINE,)),
          ("fine_preprocess.merge_feat.weight", (C_FINE, 2 * C_FINE)), ("fine_preprocess.merge_feat.bias", (C_FINE,)))
 _PROBE = _KEYS[0][0]
-
-
-def _pixels(cell, w, pair, P, scale, tf, name, offset=None, rounded=True):
-    """CoarseMatches.to_pixels' cell -> pixel, with an offset [M,2] f64 added in the descriptor image's
-    frame before the transform's inverse."""
-    xy = torch.stack([cell % w, torch.div(cell, w, rounding_mode="floor")], 1).to(torch.float64) * float(scale)
-    if offset is not None:
-        xy = xy + offset
-    if tf is not None:
-        T = tf if torch.is_tensor(tf) else torch.from_numpy(np.array(tf, dtype=np.float64))
-        T = T.detach().to(torch.float64).cpu()
-        if tuple(T.shape) == (3, 3):
-            T = T[None].expand(P, 3, 3)
-        if tuple(T.shape) != (P, 3, 3):
-            raise ValueError(f"to_pixels: {name} must be [3,3] or [{P},3,3], got {tuple(T.shape)}")
-        Ti = torch.linalg.inv(T).to(cell.device)[pair]                  # [M,3,3]
-        q = (Ti[:, :, 0] * xy[:, 0:1] + Ti[:, :, 1] * xy[:, 1:2]) + Ti[:, :, 2]
-        xy = q[:, :2] / q[:, 2:3]
-    return _round_half_away(xy) if rounded else xy
 
 
 @dataclass
@@ -77,21 +59,12 @@ class FineMatches:
         P = self.pair_start.numel() - 1
         pair = self.pair.to(torch.int64)
         offset = self.expec[:, :2].to(torch.float64) * float((WINDOW // 2) * scale_f)
-        uv_a = _pixels(self.i.to(torch.int64), self.hw_a[1], pair, P, scale, tf_a, "tf_a", None, rounded)
-        uv_b = _pixels(self.j.to(torch.int64), self.hw_b[1], pair, P, scale, tf_b, "tf_b", offset, rounded)
+        uv_a = cells_to_pixels(self.i.to(torch.int64), self.hw_a[1], pair, P, scale, tf_a, "tf_a", None, rounded)
+        uv_b = cells_to_pixels(self.j.to(torch.int64), self.hw_b[1], pair, P, scale, tf_b, "tf_b", offset, rounded)
         return uv_a, uv_b, self.pair_start, self.conf
 
 
-def _find_prefix(sd):
-    found = [k[:-len(_PROBE)] for k in sd if k.endswith(_PROBE)]
-    if len(found) == 1:
-        return found[0]
-    if not found:
-        raise ValueError(f"FineRefiner: key {_PROBE!r} is missing under every prefix")
-    raise ValueError(f"FineRefiner: prefixes {sorted(found)} all hold a fine stage, name one")
-
-
-class FineRefiner:
+class FineRefiner(PackedWeights):
     """FinePreprocess, loftr_fine and FineMatching with their weights packed for the device.
 
     weights maps the reference's parameter names (fine_preprocess.down_proj.{weight,bias} [128,256],
@@ -102,52 +75,35 @@ class FineRefiner:
 
     def __init__(self, weights, layer_names=("self", "cross"), device=None, prefix=""):
         what = "FineRefiner"
-        arr = {}
-        for key, shape in _KEYS:
-            if prefix + key not in weights:
-                raise ValueError(f"{what}: key {prefix + key!r} is missing")
-            v = _as_numpy(weights[prefix + key])
-            if tuple(v.shape) != shape:
-                raise ValueError(f"{what}: key {prefix + key!r} has shape {tuple(v.shape)}, expected {shape}")
-            arr[key] = v
+        arr = {key: self.lookup(weights, prefix, key, shape, what) for key, shape in _KEYS}
         wd = arr[_KEYS[0][0]].astype(np.float16)
         wm = arr[_KEYS[2][0]].astype(np.float16)
         parts = [pack_matrix(wd), pack_matrix(np.ascontiguousarray(wm[:, :C_FINE])),
                  pack_matrix(np.ascontiguousarray(wm[:, C_FINE:])),
                  np.ascontiguousarray(arr[_KEYS[1][0]].astype(np.float32)),
                  np.ascontiguousarray(arr[_KEYS[3][0]].astype(np.float32))]
-        self.packed = np.concatenate([p.view(np.uint8).ravel() for p in parts])
-        assert self.packed.size == WEIGHT_BYTES
+        packed = np.concatenate([p.view(np.uint8).ravel() for p in parts])
+        assert packed.size == WEIGHT_BYTES
         try:
             self.transformer = FeatureTransformer(weights, d_model=C_FINE, layer_names=layer_names, device=device,
                                                   prefix=prefix + "loftr_fine.")
         except ValueError as e:
             raise ValueError(str(e).replace("FeatureTransformer", what, 1)) from None
-        self._weights = {}
-        if device is not None:
-            self._device_weights(torch.device(device))
+        super().__init__(packed, device)
 
     @classmethod
     def from_state_dict(cls, sd, prefix=None, device=None, layer_names=("self", "cross")):
         """From a checkpoint's state dict. prefix is what stands before 'fine_preprocess...' and
         'loftr_fine...' ('', 'matcher.'); None finds it."""
         if prefix is None:
-            prefix = _find_prefix(sd)
+            prefix = cls.find_prefix(sd, _PROBE, "FineRefiner", "a fine stage")
         return cls(sd, layer_names=layer_names, device=device, prefix=prefix)
-
-    def _device_weights(self, dev):
-        dev = torch.device(dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._weights:
-            self._weights[dev] = torch.from_numpy(self.packed).to(dev)
-        return self._weights[dev]
 
     @staticmethod
     def _fine_map(f, name, channels_last):
         """-> (tensor, channels_last) of a fine map, still where and what it was."""
         what = "FineRefiner.refine"
-        t = f if torch.is_tensor(f) else torch.from_numpy(np.array(f))
+        t = as_tensor(f)
         if t.dim() != 4 or not t.is_floating_point():
             raise ValueError(f"{what}: {name} must be a floating-point [N,{C_FINE},hf,wf] or [N,hf,wf,{C_FINE}], got "
                              f"{tuple(t.shape)} {t.dtype}")
@@ -156,7 +112,7 @@ class FineRefiner:
         if t.shape[3 if channels_last else 1] != C_FINE:
             raise ValueError(f"{what}: {name} is {tuple(t.shape)}: {C_FINE} channels are needed on axis "
                              f"{3 if channels_last else 1}")
-        return t.detach(), channels_last
+        return t, channels_last
 
     def refine(self, cm, fine_a, fine_b, coarse_a, coarse_b, frames_a=None, frames_b=None, chunk=8192, channels_last=None):
         """Refine every match of cm (a CoarseMatches of P pairs) -> FineMatches.
@@ -198,10 +154,10 @@ class FineRefiner:
         stride = strides[0]
         coarse = []
         for c, n, name in ((coarse_a, L, "coarse_a"), (coarse_b, S, "coarse_b")):
-            t = c if torch.is_tensor(c) else torch.from_numpy(np.array(c))
+            t = as_tensor(c)
             if not t.is_floating_point() or tuple(t.shape) != (P, n, C_COARSE):
                 raise ValueError(f"{what}: {name} must be a floating-point {[P, n, C_COARSE]}, got {tuple(t.shape)} {t.dtype}")
-            coarse.append(t.detach())
+            coarse.append(t)
         frames = []
         for fr, t, name in ((frames_a, fa, "frames_a"), (frames_b, fb, "frames_b")):
             N = t.shape[0]
@@ -210,16 +166,14 @@ class FineRefiner:
                     raise ValueError(f"{what}: fine_{name[-1]} holds {N} maps for {P} pairs: give {name}")
                 frames.append(None)
                 continue
-            v = fr if torch.is_tensor(fr) else torch.from_numpy(np.array(fr))
+            v = as_tensor(fr)
             if v.dim() != 1 or v.numel() != P or v.is_floating_point() or v.dtype == torch.bool:
                 raise ValueError(f"{what}: {name} must be {[P]} integers, got {tuple(v.shape)} {v.dtype}")
             if not v.is_cuda and v.numel() and (int(v.min()) < 0 or int(v.max()) >= N):
                 raise ValueError(f"{what}: {name} must lie in 0 .. {N - 1}")
-            frames.append(v.detach())
+            frames.append(v)
 
-        dev = cm.j_of_i.device
-        if not dev.type == "cuda":
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = default_device(cm.j_of_i)
         lib = _lib.lib()
         i32, f32, i64 = torch.int32, torch.float32, torch.int64
         with torch.cuda.device(dev):
@@ -273,7 +227,7 @@ class FineRefiner:
         D.pair, D.i, D.j = (_lib.ptr(x) for x in idx)
         D.M, D.P, D.N_a, D.N_b = idx[0].numel(), P, maps[0].shape[0], maps[1].shape[0]
         D.h0, D.w0, D.h1, D.w1, D.stride = hw_a[0], hw_a[1], hw_b[0], hw_b[1], stride
-        w = self._device_weights(win_a.device)
+        w = self.device_weights(win_a.device)
         D.weights, D.weights_bytes = _lib.ptr(w), w.numel()
         D.context, D.win_a, D.win_b = _lib.ptr(ctx), _lib.ptr(win_a), _lib.ptr(win_b)
         _lib.check(lib.nof_fine_windows(ctypes.byref(D), stream), what)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_host, as_tensor, default_device
 
 __all__ = ["prepare_frames", "erode_depth", "bilateral_depth", "depth_geometry", "lift_matches", "covisibility", "relative_poses",
            "FrameMaps", "LiftedMatches", "MAX_RADIUS", "TILE"]
@@ -69,11 +70,11 @@ class LiftedMatches:
 
 def _images(a, dtype, what, name):
     """a (array or tensor, [H,W] or [N,H,W]) -> ([N,H,W] tensor of dtype on the device it came from, single)."""
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a))       # a copy: a may be read-only
+    t = as_tensor(a)
     if t.dim() not in (2, 3):
         raise ValueError(f"{what}: {name} must be [H,W] or [N,H,W], got {tuple(t.shape)}")
     single = t.dim() == 2
-    t = t.detach()[None] if single else t.detach()
+    t = t[None] if single else t
     N, H, W = t.shape
     if N < 1 or N > 65535 or H < 1 or W < 1 or N * H * W >= 2 ** 31:
         raise ValueError(f"{what}: {name} of {N}x{H}x{W} (N in 1 .. 65535, H, W at least 1, N*H*W < 2^31)")
@@ -99,14 +100,9 @@ def _numbers(what, **kw):
     return out
 
 
-def _device(t, device):
-    return torch.device(device) if device is not None else (
-        t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-
-
 def _intrinsics(K, N, what):
     """K [3,3] or [N,3,3], finite, zero skew, the last row (0,0,1) -> [N,4] f64 (fx, fy, cx, cy) on the host."""
-    Kh = (K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)).astype(np.float64)
+    Kh = as_host(K, np.float64)
     if Kh.shape not in ((3, 3), (N, 3, 3)):
         raise ValueError(f"{what}: K must be [3,3] or [{N},3,3], got {Kh.shape}")
     Kn = np.broadcast_to(Kh, (N, 3, 3))
@@ -117,6 +113,39 @@ def _intrinsics(K, N, what):
     if (Kn[:, 0, 0] == 0).any() or (Kn[:, 1, 1] == 0).any():
         raise ValueError(f"{what}: K has a zero focal length")
     return Kh, np.ascontiguousarray(np.stack([Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2]], 1))
+
+
+def _erode_params(what, radius, diff, ratio, pre=""):
+    """erode_depth's own parameters, under the names `pre` gives them -> (radius, what _numbers has still to
+    check). Every caller validates in two steps, all integers and then all numbers, so that a refusal
+    does not depend on which stage an argument belongs to."""
+    return _radius(radius, what, pre + "radius"), {pre + "diff": diff, pre + "ratio": ratio}
+
+
+def _bilateral_params(what, radius, passes, sigma_d, sigma_r, band, pre=""):
+    """bilateral_depth's own parameters -> (radius, passes, what _numbers has still to check); _sigmas follows it."""
+    radius = _radius(radius, what, pre + "radius")
+    passes = int(passes)
+    if passes < 0:
+        raise ValueError(f"{what}: {pre}passes={passes} must not be negative")
+    return radius, passes, {"sigma_d": sigma_d, "sigma_r": sigma_r, pre + "band": band}
+
+
+def _sigmas(what, sigma_d, sigma_r):
+    if not sigma_d > 0 or not sigma_r > 0:
+        raise ValueError(f"{what}: sigma_d={sigma_d} and sigma_r={sigma_r} must be positive")
+
+
+def _geometry_params(what, d, K, mask, z_diff, edge_angle_deg):
+    """depth_geometry's own parameters for the depth images d [N,H,W] -> (K as given in f64, [N,4] f64, the mask
+    [N,H,W] u8 or None, what _numbers has still to check)."""
+    Kh, K4 = _intrinsics(K, d.shape[0], what)
+    m = None
+    if mask is not None:
+        m, _ = _images(mask, torch.uint8, what, "mask")
+        if m.shape != d.shape:
+            raise ValueError(f"{what}: mask is {tuple(m.shape)}, depth {tuple(d.shape)}")
+    return Kh, K4, m, {"z_diff": z_diff, "edge_angle_deg": edge_angle_deg}
 
 
 def _erode(L, d, radius, depth_min, zfar, diff, ratio):
@@ -163,9 +192,9 @@ def erode_depth(depth, *, zfar=1.0, depth_min=0.1, radius=1, diff=0.001, ratio=0
     counted). depth [H,W] or [N,H,W] -> a float32 device tensor of the same shape."""
     what = "erode_depth"
     d, single = _images(depth, torch.float32, what, "depth")
-    radius = _radius(radius, what, "radius")
-    depth_min, zfar, diff, ratio = _numbers(what, depth_min=depth_min, zfar=zfar, diff=diff, ratio=ratio)
-    dev = _device(d, device)
+    radius, numbers = _erode_params(what, radius, diff, ratio)
+    depth_min, zfar, diff, ratio = _numbers(what, depth_min=depth_min, zfar=zfar, **numbers)
+    dev = default_device(d, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
         out = _erode(L, d.to(dev), radius, depth_min, zfar, diff, ratio)
@@ -179,15 +208,10 @@ def bilateral_depth(depth, *, zfar=1.0, depth_min=0.1, radius=2, sigma_d=2.0, si
     reference. With return_passes the image after every pass comes back as a list."""
     what = "bilateral_depth"
     d, single = _images(depth, torch.float32, what, "depth")
-    radius = _radius(radius, what, "radius")
-    passes = int(passes)
-    if passes < 0:
-        raise ValueError(f"{what}: passes={passes} must not be negative")
-    depth_min, zfar, sigma_d, sigma_r, band = _numbers(what, depth_min=depth_min, zfar=zfar, sigma_d=sigma_d,
-                                                       sigma_r=sigma_r, band=band)
-    if not sigma_d > 0 or not sigma_r > 0:
-        raise ValueError(f"{what}: sigma_d={sigma_d} and sigma_r={sigma_r} must be positive")
-    dev = _device(d, device)
+    radius, passes, numbers = _bilateral_params(what, radius, passes, sigma_d, sigma_r, band)
+    depth_min, zfar, sigma_d, sigma_r, band = _numbers(what, depth_min=depth_min, zfar=zfar, **numbers)
+    _sigmas(what, sigma_d, sigma_r)
+    dev = default_device(d, device)
     L = _lib.lib()
     outs = []
     with torch.cuda.device(dev):
@@ -204,15 +228,9 @@ def depth_geometry(depth, K, mask=None, *, depth_min=0.1, z_diff=0.02, edge_angl
     skew; mask [H,W] or [N,H,W] of any dtype, 0 drops the pixel."""
     what = "depth_geometry"
     d, single = _images(depth, torch.float32, what, "depth")
-    N, H, W = d.shape
-    Kh, K4 = _intrinsics(K, N, what)
-    m = None
-    if mask is not None:
-        m, _ = _images(mask, torch.uint8, what, "mask")
-        if m.shape != d.shape:
-            raise ValueError(f"{what}: mask is {tuple(m.shape)}, depth {tuple(d.shape)}")
-    depth_min, z_diff, edge = _numbers(what, depth_min=depth_min, z_diff=z_diff, edge_angle_deg=edge_angle_deg)
-    dev = _device(d, device)
+    Kh, K4, m, numbers = _geometry_params(what, d, K, mask, z_diff, edge_angle_deg)
+    depth_min, z_diff, edge = _numbers(what, depth_min=depth_min, **numbers)
+    dev = default_device(d, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
         out = _geometry(L, d.to(dev), K4, None if m is None else m.to(dev), depth_min, z_diff,
@@ -232,23 +250,14 @@ def prepare_frames(depth, K, mask=None, *, zfar=1.0, depth_min=0.1, erode_radius
     (one image per pass)."""
     what = "prepare_frames"
     d, single = _images(depth, torch.float32, what, "depth")
-    N = d.shape[0]
-    Kh, K4 = _intrinsics(K, N, what)
-    m = None
-    if mask is not None:
-        m, _ = _images(mask, torch.uint8, what, "mask")
-        if m.shape != d.shape:
-            raise ValueError(f"{what}: mask is {tuple(m.shape)}, depth {tuple(d.shape)}")
-    er, br = _radius(erode_radius, what, "erode_radius"), _radius(bilateral_radius, what, "bilateral_radius")
-    passes = int(bilateral_passes)
-    if passes < 0:
-        raise ValueError(f"{what}: bilateral_passes={passes} must not be negative")
+    Kh, K4, m, g_numbers = _geometry_params(what, d, K, mask, z_diff, edge_angle_deg)
+    er, e_numbers = _erode_params(what, erode_radius, erode_diff, erode_ratio, "erode_")
+    br, passes, b_numbers = _bilateral_params(what, bilateral_radius, bilateral_passes, sigma_d, sigma_r, bilateral_band,
+                                              "bilateral_")
     depth_min, zfar, diff, ratio, sigma_d, sigma_r, band, z_diff, edge = _numbers(
-        what, depth_min=depth_min, zfar=zfar, erode_diff=erode_diff, erode_ratio=erode_ratio, sigma_d=sigma_d,
-        sigma_r=sigma_r, bilateral_band=bilateral_band, z_diff=z_diff, edge_angle_deg=edge_angle_deg)
-    if not sigma_d > 0 or not sigma_r > 0:
-        raise ValueError(f"{what}: sigma_d={sigma_d} and sigma_r={sigma_r} must be positive")
-    dev = _device(d, device)
+        what, depth_min=depth_min, zfar=zfar, **e_numbers, **b_numbers, **g_numbers)
+    _sigmas(what, sigma_d, sigma_r)
+    dev = default_device(d, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
         e = b = _erode(L, d.to(dev), er, depth_min, zfar, diff, ratio)
@@ -292,17 +301,16 @@ def _maps(maps, what):
 
 
 def _poses(poses, N, what):
-    T = poses if torch.is_tensor(poses) else torch.from_numpy(np.array(poses))
+    T = as_tensor(poses)
     if tuple(T.shape) != (N, 4, 4):
         raise ValueError(f"{what}: poses must be [{N},4,4], got {tuple(T.shape)}")
-    return T.detach().to(torch.float64).contiguous()
+    return T.to(torch.float64).contiguous()
 
 
 def _pairs(pairs, N, what, name, lo, allow_self):
-    pf = (pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else np.asarray(pairs))
+    pf = as_host(pairs, np.int64)
     if pf.ndim != 2 or pf.shape[1] != 2:
         raise ValueError(f"{what}: {name} must be [*,2], got {pf.shape}")
-    pf = pf.astype(np.int64)
     if len(pf) < lo or len(pf) > 65535:
         raise ValueError(f"{what}: {len(pf)} pairs ({lo} .. 65535)")
     if (pf < 0).any() or (pf >= N).any():
@@ -327,10 +335,10 @@ def lift_matches(maps, pair_frames, uv_a, uv_b, pair_start=None, *, poses=None, 
     P = len(pf)
 
     def rows(a, name):
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float64))
+        t = as_tensor(a, np.float64)
         if t.dim() != 2 or t.shape[1] != 2:
             raise ValueError(f"{what}: {name} must be [M,2], got {tuple(t.shape)}")
-        return t.detach().to(torch.float64).contiguous()
+        return t.to(torch.float64).contiguous()
 
     ua, ub = rows(uv_a, "uv_a"), rows(uv_b, "uv_b")
     M = len(ua)
@@ -343,8 +351,7 @@ def lift_matches(maps, pair_frames, uv_a, uv_b, pair_start=None, *, poses=None, 
             raise ValueError(f"{what}: pair_start is needed for {P} pairs")
         ps = np.array([0, M], np.int64)
     else:
-        ps = (pair_start.detach().cpu().numpy() if torch.is_tensor(pair_start) else np.asarray(pair_start))
-        ps = ps.astype(np.int64).reshape(-1)
+        ps = as_host(pair_start, np.int64).reshape(-1)
     if ps.shape != (P + 1,) or ps[0] != 0 or ps[-1] != M or (np.diff(ps) < 0).any():
         raise ValueError(f"{what}: pair_start must be [{P + 1}], start at 0, never decrease and end at M={M}")
     if poses is None and (max_dist is not None or max_normal_deg is not None):
@@ -359,7 +366,7 @@ def lift_matches(maps, pair_frames, uv_a, uv_b, pair_start=None, *, poses=None, 
         (deg,), gate_normal = _numbers(what, max_normal_deg=max_normal_deg), 1
         cosn = math.cos(math.radians(deg))
 
-    dev = _device(pts, None)
+    dev = default_device(pts)
     L = _lib.lib()
     f64 = torch.float64
     with torch.cuda.device(dev):
@@ -400,7 +407,7 @@ def covisibility(maps, poses, pairs, *, visible_angle_deg=70.0, stride=2, depth_
     Th = _poses(poses, N, what).cpu().numpy()
     depth_min, ang = _numbers(what, depth_min=depth_min, visible_angle_deg=visible_angle_deg)
     T = np.ascontiguousarray(relative_poses(Th, pf))
-    dev = _device(pts, None)
+    dev = default_device(pts)
     L = _lib.lib()
     with torch.cuda.device(dev):
         pts, nrm = pts.to(dev), nrm.to(dev)

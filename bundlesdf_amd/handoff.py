@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_tensor, default_device
 from .mesh import mesh_to_real_world  # noqa: F401  (Utils.py:508 re-export)
 
 GLCAM_IN_CVCAM = np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]], dtype=np.float64)
@@ -44,22 +45,17 @@ __all__ = ["PointCloud", "toOpen3dCloud", "depth2xyzmap", "compute_scene_bounds_
            "mesh_to_real_world", "GLCAM_IN_CVCAM"]
 
 
-def _dev(device=None):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 class PointCloud:
     """Device point cloud with the open3d.geometry.PointCloud surface the hand-off uses."""
 
     def __init__(self, points=None, colors=None, device=None):
-        self.device = _dev(device)
+        self.device = default_device(device=device)
         self._p = self._as_dev(points) if points is not None else torch.zeros((0, 3), dtype=torch.float64,
                                                                                   device=self.device)
         self._c = self._as_dev(colors) if colors is not None else None
 
     def _as_dev(self, a):
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
-        return t.to(self.device, torch.float64).reshape(-1, 3).contiguous()
+        return as_tensor(a, np.float64).to(self.device, torch.float64).reshape(-1, 3).contiguous()
 
     # -- open3d-style attributes
     @property
@@ -186,7 +182,7 @@ def toOpen3dCloud(points, colors=None, normals=None, device=None):
 def depth2xyzmap(depth, K, device=None):
     """Utils.py:219-231 on the device: camera-frame xyz per pixel (f64 math,
     f32 result), zeros where depth < 0.1. Returns a [H,W,3] f32 tensor."""
-    dev = _dev(device)
+    dev = default_device(device=device)
     z = torch.as_tensor(np.asarray(depth, np.float64), device=dev).reshape(depth.shape[0], depth.shape[1])
     H, W = z.shape
     vs = torch.arange(H, dtype=torch.float64, device=dev)[:, None].expand(H, W)
@@ -207,7 +203,7 @@ def compute_scene_bounds_worker(color_file, K, glcam_in_world, use_mask, rgb=Non
     if rgb is None:
         raise NotImplementedError("compute_scene_bounds_worker: reading frames from files is out of scope; "
                                   "pass rgb / depth / mask arrays")
-    dev = _dev(device)
+    dev = default_device(device=device)
     depth = np.asarray(depth).reshape(np.asarray(depth).shape[:2])
     xyz = depth2xyzmap(depth, K, dev)
     valid = torch.as_tensor(depth >= 0.1, device=dev)
@@ -231,7 +227,7 @@ def dbscan_labels(pts, eps, min_samples=1, device=None):
     """sklearn.cluster.DBSCAN(eps, min_samples).fit(pts).labels_ on the device
     (nof_dbscan): clusters numbered 0.. in the order of their lowest core-point
     index, -1 = noise."""
-    dev = _dev(device)
+    dev = default_device(device=device)
     p = torch.as_tensor(np.ascontiguousarray(np.asarray(pts, np.float64).reshape(-1, 3)), device=dev)
     n = len(p)
     if n == 0:
@@ -313,7 +309,7 @@ def compute_scene_bounds(color_files, glcam_in_worlds, K, use_mask=True, base_di
     assert color_files is None or rgbs is None
     if rgbs is None:
         raise NotImplementedError("compute_scene_bounds: reading frames from files is out of scope; pass rgbs/depths/masks")
-    dev = _dev(device)
+    dev = default_device(device=device)
     pcd_all = None
     for i in range(len(rgbs)):
         r = compute_scene_bounds_worker(None, K, glcam_in_worlds[i], use_mask, rgbs[i], depths[i], masks[i], dev)

@@ -8,6 +8,7 @@ every kernel is behind one of those four. The backbone runs once per distinct fr
 import numpy as np
 import torch
 
+from ._args import as_tensor
 from .backbone import Backbone
 from .fine import FineRefiner
 from .matching import match_descriptors
@@ -33,10 +34,10 @@ class Loftr:
         """images [N,H,W] or [N,1,H,W] (grey / 255), pairs [P,2] frame indices (a, b), masks [N, H/8, W/8] or
         [N, H/8 W/8] or None (0 = the coarse cell takes no part) -> the FineMatches of the P pairs."""
         what = "Loftr.match"
-        p = pairs if torch.is_tensor(pairs) else torch.from_numpy(np.asarray(pairs))
+        p = as_tensor(pairs)
         if p.dim() != 2 or p.shape[1] != 2 or p.shape[0] < 1 or p.is_floating_point() or p.dtype == torch.bool:
             raise ValueError(f"{what}: pairs must be [P,2] integers with P >= 1, got {tuple(p.shape)} {p.dtype}")
-        p = p.detach().cpu().to(torch.int64)
+        p = p.cpu().to(torch.int64)
         # the distinct frames, in order of their index; pairs renumbered to them
         frames, local = torch.unique(p, return_inverse=True)
         n_images = images.shape[0]
@@ -47,7 +48,7 @@ class Loftr:
         ia, ib = local[:, 0].to(tok.device), local[:, 1].to(tok.device)
         ma = mb = None
         if masks is not None:
-            m = masks if torch.is_tensor(masks) else torch.from_numpy(np.asarray(masks))
+            m = as_tensor(masks)
             if m.shape[0] != n_images or m[0].numel() != hw[0] * hw[1]:
                 raise ValueError(f"{what}: masks must be [{n_images},{hw[0]},{hw[1]}], got {tuple(m.shape)}")
             m = (m.reshape(n_images, -1) != 0)[frames.to(m.device)].to(tok.device)

@@ -16,21 +16,16 @@ import math
 from dataclasses import dataclass
 from typing import Optional
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_tensor, cells_to_pixels, default_device
 
 __all__ = ["match_descriptors", "CoarseMatches", "MAX_PAIRS", "MAX_C", "TILE"]
 
 MAX_PAIRS = 65535
 MAX_C = 512
 TILE = (128, 32)        # MATCH_QB, MATCH_KT of csrc/match.hip: queries of a block, keys of a staged tile
-
-
-def _round_half_away(x):
-    """C round(): halves go away from zero, as lift_matches rounds its coordinates."""
-    return torch.sign(x) * torch.floor(torch.abs(x) + 0.5)
 
 
 @dataclass
@@ -58,34 +53,19 @@ class CoarseMatches:
         j = self.j_of_i[pair, i].to(torch.int64)
         counts = torch.bincount(pair, minlength=P)
         pair_start = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]).to(torch.int32)
-
-        def pixels(cell, w, tf, name):
-            xy = torch.stack([cell % w, torch.div(cell, w, rounding_mode="floor")], 1).to(torch.float64) * float(scale)
-            if tf is not None:
-                T = tf if torch.is_tensor(tf) else torch.from_numpy(np.array(tf, dtype=np.float64))
-                T = T.detach().to(torch.float64).cpu()
-                if tuple(T.shape) == (3, 3):
-                    T = T[None].expand(P, 3, 3)
-                if tuple(T.shape) != (P, 3, 3):
-                    raise ValueError(f"to_pixels: {name} must be [3,3] or [{P},3,3], got {tuple(T.shape)}")
-                Ti = torch.linalg.inv(T).to(dev)[pair]                   # [M,3,3]
-                q = (Ti[:, :, 0] * xy[:, 0:1] + Ti[:, :, 1] * xy[:, 1:2]) + Ti[:, :, 2]
-                xy = q[:, :2] / q[:, 2:3]
-            return _round_half_away(xy)
-
-        return (pixels(i, self.hw_a[1], tf_a, "tf_a"), pixels(j, self.hw_b[1], tf_b, "tf_b"), pair_start,
-                self.conf[pair, i])
+        return (cells_to_pixels(i, self.hw_a[1], pair, P, scale, tf_a, "tf_a"),
+                cells_to_pixels(j, self.hw_b[1], pair, P, scale, tf_b, "tf_b"), pair_start, self.conf[pair, i])
 
 
 def _descriptors(d, name):
     """(fp16 tensor [P,n,C] on the device it came from, single): float32 is rounded once with .half()."""
-    t = d if torch.is_tensor(d) else torch.from_numpy(np.array(d))        # a copy: d may be read-only
+    t = as_tensor(d)
     if not t.is_floating_point():
         raise ValueError(f"match_descriptors: {name} must be a floating-point array, got {t.dtype}")
     if t.dim() not in (2, 3):
         raise ValueError(f"match_descriptors: {name} must be [n,C] or [P,n,C], got {tuple(t.shape)}")
     single = t.dim() == 2
-    t = t.detach()[None] if single else t.detach()
+    t = t[None] if single else t
     return t.half().contiguous(), single
 
 
@@ -100,8 +80,8 @@ def _grid(hw, n, name, count):
 
 
 def _mask(v, shape, single, name):
-    t = v if torch.is_tensor(v) else torch.from_numpy(np.array(v))
-    t = t.detach()[None] if (single and t.dim() == 1) else t.detach()
+    t = as_tensor(v)
+    t = t[None] if (single and t.dim() == 1) else t
     if tuple(t.shape) != shape:
         raise ValueError(f"match_descriptors: {name} must be {list(shape)}, got {tuple(t.shape)}")
     return (t != 0).to(torch.uint8).contiguous()
@@ -158,7 +138,7 @@ def match_descriptors(desc_a, desc_b, hw_a, hw_b, valid_a=None, valid_b=None, *,
             if torch.is_tensor(v) and torch.is_tensor(desc_a) and v.device != desc_a.device:
                 raise ValueError(f"{what}: {name} is on {v.device} and desc_a on {desc_a.device}")
 
-    dev = a.device if a.is_cuda else (b.device if b.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    dev = default_device(a if a.is_cuda else b)
     lib = _lib.lib()
     i32, f32 = torch.int32, torch.float32
     with torch.cuda.device(dev):

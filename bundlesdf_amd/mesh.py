@@ -23,6 +23,8 @@ own corner signs, so neighbouring cubes agree and the surface is watertight.
 import numpy as np
 import torch
 
+from ._args import as_tensor, default_device
+
 # corner c of a cube = offset (c & 1, c >> 1 & 1, c >> 2 & 1) along (i, j, k)
 _CORNERS = np.array([[(c >> d) & 1 for d in range(3)] for c in range(8)])
 # edge e = (corner with bit `axis` clear, axis): 4 per axis
@@ -175,12 +177,12 @@ class Mesh:
         over the vertex -> face CSR; "scipy": the same sums in numpy on the host."""
         _check_backend("compute_vertex_normals", backend)
         V = len(self.vertices)
-        dev = _device() if backend == "hip" else torch.device("cpu")
+        dev = default_device() if backend == "hip" else torch.device("cpu")
         faces = _checked_faces("compute_vertex_normals", self.faces, V, dev)
         row_start, face_ids = vertex_faces(faces, V, device=dev)
         if backend == "hip":
             from . import _lib
-            v = torch.from_numpy(np.array(self.vertices, np.float64)).to(dev)
+            v = as_tensor(self.vertices, np.float64).to(dev)
             f32 = faces.to(torch.int32).contiguous()
             out = torch.empty_like(v)
             with torch.cuda.device(dev):
@@ -452,7 +454,7 @@ def marching_cubes_device(volume, level=0.0):
     from . import _lib
     vol = torch.as_tensor(volume)
     if not vol.is_cuda:
-        vol = vol.to(torch.device("cuda", torch.cuda.current_device()))
+        vol = vol.to(default_device())
     vol = vol.float().contiguous()
     if vol.dim() != 3:
         raise ValueError(f"marching_cubes_device: volume must be [N0,N1,N2], got {tuple(vol.shape)}")
@@ -495,9 +497,7 @@ def component_labels(faces, n_vertices, device=None):
     nothing, reading one flag per sweep."""
     from . import _lib
     f = torch.as_tensor(faces)
-    if device is None:
-        device = f.device if f.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    f = f.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    f = f.to(device=default_device(f, device), dtype=torch.int32).reshape(-1, 3).contiguous()
     n = int(n_vertices)
     if len(f) and (int(f.min()) < 0 or int(f.max()) >= n):
         raise ValueError(f"component_labels: face corners must be in [0, {n})")
@@ -636,14 +636,9 @@ def _check_backend(what, backend):
         raise ValueError(f"{what}: backend must be 'scipy' or 'hip', got {backend!r}")
 
 
-def _device(device=None):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def _checked_faces(what, faces, n_vertices, device):
     """faces as an int64 [F,3] tensor on `device`; ValueError for a corner outside [0, n_vertices)."""
-    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.array(faces, np.int64))   # a writable copy
-    f = f.to(device=device, dtype=torch.int64).reshape(-1, 3)
+    f = as_tensor(faces, np.int64).to(device=device, dtype=torch.int64).reshape(-1, 3)
     n = int(n_vertices)
     if n < 0 or n * 3 >= 1 << 31 or len(f) * 3 >= 1 << 31:
         raise ValueError(f"{what}: {n} vertices, {len(f)} faces: both times 3 must be below 2^31")
@@ -667,9 +662,7 @@ def vertex_adjacency(faces, n_vertices, device=None):
     device tensor, else the current HIP device): row v holds the distinct vertices that share a face
     edge with v, ascending. An edge shared by several faces counts once; the self-edge of a degenerate
     face (a, a, b) is dropped; a corner outside [0, n_vertices) raises ValueError."""
-    if device is None and torch.is_tensor(faces) and faces.is_cuda:
-        device = faces.device
-    f = _checked_faces("vertex_adjacency", faces, n_vertices, _device(device))
+    f = _checked_faces("vertex_adjacency", faces, n_vertices, default_device(faces, device))
     a = torch.cat([f[:, [0, 1, 2]].reshape(-1), f[:, [1, 2, 0]].reshape(-1)])   # every face edge, both directions
     b = torch.cat([f[:, [1, 2, 0]].reshape(-1), f[:, [0, 1, 2]].reshape(-1)])
     keep = a != b
@@ -679,9 +672,7 @@ def vertex_adjacency(faces, n_vertices, device=None):
 def vertex_faces(faces, n_vertices, device=None):
     """The vertex -> face CSR (row_start [V+1], face_ids) int32 on `device`, by vertex_adjacency's routine
     keyed (vertex, face): the faces of v, each once, in ascending face index."""
-    if device is None and torch.is_tensor(faces) and faces.is_cuda:
-        device = faces.device
-    f = _checked_faces("vertex_faces", faces, n_vertices, _device(device))
+    f = _checked_faces("vertex_faces", faces, n_vertices, default_device(faces, device))
     ids = torch.arange(len(f), dtype=torch.int64, device=f.device)[:, None].expand(-1, 3).reshape(-1)
     return _csr(f.reshape(-1), ids, n_vertices, len(f))
 
@@ -704,7 +695,7 @@ def mesh_volume(mesh_or_vertices, faces=None, backend="hip"):
         f = _checked_faces("mesh_volume", faces, len(vertices), torch.device("cpu")).numpy()
         return _volume_host(vertices, f)
     from . import _lib
-    dev = _device()
+    dev = default_device()
     f = _checked_faces("mesh_volume", faces, len(vertices), dev).to(torch.int32).contiguous()
     v = torch.from_numpy(vertices).to(dev)
     L = _lib.lib()
@@ -721,14 +712,14 @@ def _smooth_hip(vertices, faces, factors, volume_constraint):
     nof_mesh_laplacian_step, with the constraint followed by nof_mesh_volume and nof_mesh_scale_to_volume
     towards the initial volume. One host read at the end: the vertices with the initial volume and the flag."""
     from . import _lib
-    dev = _device()
+    dev = default_device()
     V = len(vertices)
     f = _checked_faces("filter", faces, V, dev)
     row_start, cols = vertex_adjacency(f, V, device=dev)
     f32 = f.to(torch.int32).contiguous()
     L = _lib.lib()
     with torch.cuda.device(dev):
-        a = torch.from_numpy(np.array(vertices, np.float64)).to(dev)
+        a = as_tensor(vertices, np.float64).to(dev)
         b = torch.empty_like(a)
         vol0, vol = torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)

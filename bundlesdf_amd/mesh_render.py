@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import default_device
 
 # Faces whose clamped screen bounding box holds at most this many pixels are rasterised by their own
 # lane; larger ones by a wave each. Chosen from scripts/render_mesh.py's table on one MI355X
@@ -33,7 +34,7 @@ class MeshRenderer:
 
     def __init__(self, mesh, K, H, W, znear=0.1, zfar=2.0, device=None):
         from .mesh import _checked_faces
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = default_device(device=device)
         self.device = dev
         self.H, self.W, self.znear, self.zfar = int(H), int(W), float(znear), float(zfar)
         self.K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_host, as_tensor, default_device
 
 __all__ = ["mask_roi", "rotate_image_transform", "rotation_about_axis_z", "pair_transforms", "invert_affine",
            "warp_images", "pair_crops", "find_corres", "PairCrops", "Correspondences", "CELL", "MAX_SIDE", "TILE"]
@@ -70,24 +71,15 @@ def _check_sizes(what, out_size, margin):
     return int(out_size), None if margin is None else int(margin)
 
 
-def _host(a, dtype):
-    return (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(dtype)
-
-
-def _device(t, device):
-    return torch.device(device) if device is not None else (
-        t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-
-
 def _masks_u8(masks, what):
     """masks (array or tensor, [H,W] or [N,H,W], bool or integer) -> ([N,H,W] u8 tensor, 1 = foreground, single)."""
-    t = masks if torch.is_tensor(masks) else torch.from_numpy(np.array(masks))      # a copy: masks may be read-only
+    t = as_tensor(masks)
     if t.dim() not in (2, 3):
         raise ValueError(f"{what}: masks must be [H,W] or [N,H,W], got {tuple(t.shape)}")
     if t.is_floating_point() or t.is_complex():
         raise ValueError(f"{what}: masks must be bool or an integer type, got {t.dtype}")
     single = t.dim() == 2
-    t = t.detach()[None] if single else t.detach()
+    t = t[None] if single else t
     N, H, W = t.shape
     if N > 65535 or H < 1 or W < 1 or N * H * W >= 2 ** 31:
         raise ValueError(f"{what}: masks of {N}x{H}x{W} (N at most 65535, H, W at least 1, N*H*W < 2^31)")
@@ -109,7 +101,7 @@ def mask_roi(masks, device=None):
     integer type, non-zero = foreground -> (roi [N,4] i32 = (umin, umax, vmin, vmax), inclusive; count [N]
     i32), device tensors (without N for a single mask). An empty mask gives (W, -1, H, -1) and 0."""
     m, single = _masks_u8(masks, "mask_roi")
-    dev = _device(m, device)
+    dev = default_device(m, device)
     L = _lib.lib()
     with torch.cuda.device(dev):
         roi, count = _mask_roi(L, m.to(dev))
@@ -214,16 +206,16 @@ def pair_transforms(roi, poses, pairs, H, W, out_size=400, margin=10):
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError(f"{what}: H={H}, W={W} must be at least 1")
-    r = _host(roi, np.int64)
+    r = as_host(roi, np.int64)
     if r.ndim != 2 or r.shape[1] not in (4, 5):
         raise ValueError(f"{what}: roi must be [N,4] or [N,5], got {r.shape}")
     N = len(r)
-    T = _host(poses, np.float64)
+    T = as_host(poses, np.float64)
     if T.shape != (N, 4, 4):
         raise ValueError(f"{what}: poses must be [{N},4,4], got {T.shape}")
     if not np.isfinite(T).all():
         raise ValueError(f"{what}: poses is not finite")
-    pf = _host(pairs, np.int64)
+    pf = as_host(pairs, np.int64)
     if pf.ndim != 2 or pf.shape[1] != 2:
         raise ValueError(f"{what}: pairs must be [P,2], got {pf.shape}")
     if (pf < 0).any() or (pf >= N).any():
@@ -262,7 +254,7 @@ def invert_affine(tf):
     or [..., 2, 3]. With a b tx / c d ty: det = a d - b c, the linear part (d / det, (-b) / det, (-c) / det,
     a / det) = (i00, i01, i10, i11), and the translation (-(i00 tx + i01 ty), -(i10 tx + i11 ty))."""
     what = "invert_affine"
-    M = _host(tf, np.float64)
+    M = as_host(tf, np.float64)
     if M.ndim < 2 or M.shape[-2:] not in ((3, 3), (2, 3)):
         raise ValueError(f"{what}: tf must be [...,3,3] or [...,2,3], got {M.shape}")
     if not np.isfinite(M).all():
@@ -284,8 +276,7 @@ def invert_affine(tf):
 
 def _source(images, what):
     """images -> (contiguous tensor, format, (N, H, W)): [N,H,W] u8, [N,H,W] f32 or [N,H,W,3] u8."""
-    t = images if torch.is_tensor(images) else torch.from_numpy(np.array(images))
-    t = t.detach()
+    t = as_tensor(images)
     if t.dtype == torch.uint8 and t.dim() == 3:
         fmt = _lib.WARP_GREY_U8
     elif t.dtype == torch.float32 and t.dim() == 3:
@@ -317,12 +308,12 @@ def _warp(L, src, fmt, shape, m, inv, frames, S, cell_masks):
 
 
 def _warp_args(what, inv, frames, shape, masks):
-    inv = np.ascontiguousarray(_host(inv, np.float64))
+    inv = as_host(inv, np.float64)
     if inv.ndim != 3 or inv.shape[1:] != (2, 3):
         raise ValueError(f"{what}: inv must be [Q,2,3], got {inv.shape}")
     if not np.isfinite(inv).all():
         raise ValueError(f"{what}: inv is not finite")
-    fr = _host(frames, np.int64).reshape(-1)
+    fr = as_host(frames, np.int64).reshape(-1)
     if len(fr) != len(inv):
         raise ValueError(f"{what}: frames has {len(fr)} entries, inv {len(inv)}")
     fr = np.ascontiguousarray(np.clip(fr, -1, 2 ** 31 - 1).astype(np.int32))      # any frame outside 0 .. N-1 gives zeros
@@ -346,7 +337,7 @@ def warp_images(images, inv, frames, out_size, masks=None, cell_masks=True):
     S, _ = _check_sizes(what, out_size, None)
     src, fmt, shape = _source(images, what)
     inv, fr, m = _warp_args(what, inv, frames, shape, masks)
-    dev = _device(src, None)
+    dev = default_device(src)
     L = _lib.lib()
     with torch.cuda.device(dev):
         return _warp(L, src.to(dev), fmt, shape, None if m is None else m.to(dev), inv, fr, S, bool(cell_masks))
@@ -365,14 +356,14 @@ def pair_crops(images, masks, poses, pairs, out_size=400, margin=10, cell_masks=
     m, _ = _masks_u8(masks, what)
     if tuple(m.shape) != tuple(shape):
         raise ValueError(f"{what}: masks is {tuple(m.shape)}, images {tuple(shape)}")
-    dev = _device(src, None)
+    dev = default_device(src)
     L = _lib.lib()
     with torch.cuda.device(dev):
         src, m = src.to(dev), m.to(dev)
         roi, count = _mask_roi(L, m)
         host = torch.cat([roi, count[:, None]], 1).cpu().numpy()                   # the one host read
         tf_a, tf_b, valid = pair_transforms(host, poses, pairs, H, W, S, margin)
-        pf = _host(pairs, np.int64)
+        pf = as_host(pairs, np.int64)
         P = len(pf)
         inv = invert_affine(np.stack([tf_a, tf_b], 1).reshape(2 * P, 3, 3))
         frames = np.where(valid[:, None], pf, -1).reshape(2 * P).astype(np.int32)
@@ -406,7 +397,7 @@ def find_corres(matcher, images, masks, maps, poses, pairs, *, out_size=400, mar
     what = "find_corres"
     if ransac is not None and not isinstance(ransac, dict):
         raise ValueError(f"{what}: ransac must be None or a dict of ransac_pairs' keyword arguments")
-    if len(_host(pairs, np.int64).reshape(-1, 2)) < 1:
+    if len(as_host(pairs, np.int64).reshape(-1, 2)) < 1:
         raise ValueError(f"{what}: pairs must hold at least one pair")
     pc = pair_crops(images, masks, poses, pairs, out_size, margin, cell_masks)
     fm = matcher.match(pc.images, pc.match_pairs, pc.cells if cell_masks else None, thr=thr, border_rm=border_rm,

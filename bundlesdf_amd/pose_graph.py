@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_host, as_tensor, default_device
 
 __all__ = ["optimize_poses", "MAX_FRAMES", "MAX_RADIUS", "ROW_TILE"]
 
@@ -29,11 +30,11 @@ ROW_TILE = 256          # PG_TILE: sparse rows, or source pixels, a block takes 
 def _tensor(a, dtype, name, shape):
     """a (array or tensor) as a contiguous tensor of dtype on the device it came from; shape has None
     for a free dimension."""
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a))       # a copy: a may be read-only
+    t = as_tensor(a)
     if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
         want = ",".join("*" if s is None else str(s) for s in shape)
         raise ValueError(f"optimize_poses: {name} must be [{want}], got {tuple(t.shape)}")
-    return t.detach().to(dtype).contiguous()
+    return t.to(dtype).contiguous()
 
 
 def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_start=None, weight=None,
@@ -82,7 +83,7 @@ def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_star
     if fixed is None:
         fx[0] = True
     else:
-        f = fixed.detach().cpu().numpy() if torch.is_tensor(fixed) else np.asarray(fixed)
+        f = as_host(fixed)
         if f.shape != (N,):
             raise ValueError(f"{what}: fixed must be [{N}], got {f.shape}")
         fx = f.astype(bool)
@@ -94,10 +95,9 @@ def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_star
     if sparse:
         if pts_a is None or pts_b is None:
             raise ValueError(f"{what}: pair_frames needs pts_a and pts_b")
-        pf_h = (pair_frames.detach().cpu().numpy() if torch.is_tensor(pair_frames) else np.asarray(pair_frames))
+        pf_h = as_host(pair_frames, np.int64)
         if pf_h.ndim != 2 or pf_h.shape[1] != 2:
             raise ValueError(f"{what}: pair_frames must be [P,2], got {pf_h.shape}")
-        pf_h = pf_h.astype(np.int64)
         P = len(pf_h)
         if P < 1 or P > 65535:
             raise ValueError(f"{what}: {P} pairs (1 .. 65535)")
@@ -116,8 +116,7 @@ def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_star
                 raise ValueError(f"{what}: pair_start is needed for {P} pairs")
             ps_h = np.array([0, M], np.int64)
         else:
-            ps_h = (pair_start.detach().cpu().numpy() if torch.is_tensor(pair_start) else np.asarray(pair_start))
-            ps_h = ps_h.astype(np.int64).reshape(-1)
+            ps_h = as_host(pair_start, np.int64).reshape(-1)
         if ps_h.shape != (P + 1,) or ps_h[0] != 0 or ps_h[-1] != M or (np.diff(ps_h) < 0).any():
             raise ValueError(f"{what}: pair_start must be [{P + 1}], start at 0, never decrease and end at M={M}")
         if weight is not None:
@@ -139,7 +138,7 @@ def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_star
         nm = _tensor(normals, torch.float32, "normals", (N, H, W, 3))
         if H < 1 or W < 1 or H * W >= 2 ** 24:
             raise ValueError(f"{what}: maps of {H}x{W} (at least 1x1, H*W < 2^24)")
-        Kh = (K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)).astype(np.float64)
+        Kh = as_host(K, np.float64)
         if Kh.shape != (3, 3) or not np.isfinite(Kh).all():
             raise ValueError(f"{what}: K must be a finite [3,3], got {Kh.shape}")
         kk = np.array([Kh[0, 0], Kh[1, 1], Kh[0, 2], Kh[1, 2]])
@@ -152,8 +151,7 @@ def optimize_poses(poses, *, pair_frames=None, pts_a=None, pts_b=None, pair_star
         if float(max_rot_deg) < 180.0:
             min_trace = 1.0 + 2.0 * math.cos(math.radians(max(float(max_rot_deg), 0.0)))
 
-    dev = torch.device(device) if device is not None else (
-        T.device if T.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    dev = default_device(T, device)
     L = _lib.lib()
     f64 = torch.float64
     n = 6 * N

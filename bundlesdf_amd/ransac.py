@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import as_host, as_tensor, default_device
 from .evaluate import _kabsch
 
 __all__ = ["ransac_pairs", "inliers_per_pair", "RansacResult", "ROW_TILE", "MAX_PAIRS", "MAX_TRIALS", "MAX_CONF"]
@@ -46,12 +47,6 @@ class RansacResult:
     trial_score: Optional[torch.Tensor] = None   # [P,T] i64, fixed point (x 65536)
 
 
-def _host(a, dtype):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a, dtype))
-
-
 def _is_list(a):
     return isinstance(a, (list, tuple)) and len(a) > 0 and (torch.is_tensor(a[0]) or np.ndim(a[0]) >= 1)
 
@@ -61,8 +56,7 @@ def _rows(a, name, width):
     device it came from: everything is validated before the first device call."""
     if _is_list(a):
         return torch.cat([_rows(x, name, width) for x in a])
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float64))     # a copy: a may be read-only
-    t = t.to(torch.float64)
+    t = as_tensor(a, np.float64).to(torch.float64)
     if width:
         if t.numel() % width:
             raise ValueError(f"ransac_pairs: {name} must be [M,{width}], got {tuple(t.shape)}")
@@ -73,7 +67,7 @@ def _rows(a, name, width):
 def _per_pair(v, P, name, default):
     if v is None:
         return np.full(P, default, np.float64)
-    a = _host(v, np.float64).reshape(-1)
+    a = as_host(v, np.float64).reshape(-1)
     if a.size == 1:
         a = np.full(P, a[0])
     if a.shape != (P,):
@@ -120,7 +114,7 @@ def ransac_pairs(pts_a, pts_b, pair_start=None, normals_a=None, normals_b=None, 
     if M >= 2 ** 31:
         raise ValueError(f"ransac_pairs: {M} rows (max 2^31 - 1)")
     if not listed:
-        ps = np.array([0, M], np.int64) if pair_start is None else _host(pair_start, np.int64).reshape(-1)
+        ps = np.array([0, M], np.int64) if pair_start is None else as_host(pair_start, np.int64).reshape(-1)
     P = len(ps) - 1
     if P < 1 or P > MAX_PAIRS:
         raise ValueError(f"ransac_pairs: {P} pairs (1 .. {MAX_PAIRS})")
@@ -148,8 +142,7 @@ def ransac_pairs(pts_a, pts_b, pair_start=None, normals_a=None, normals_b=None, 
     min_trace = np.where(np.isinf(mr), -np.inf, 1.0 + 2.0 * np.cos(np.deg2rad(np.minimum(mr, 180.0))))
     cos_normal = -math.inf if normal_angle_deg is None else math.cos(math.radians(float(normal_angle_deg)))
 
-    dev = torch.device(device) if device is not None else (
-        a.device if a.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    dev = default_device(a, device)
     L = _lib.lib()
     i32, f64 = torch.int32, torch.float64
     with torch.cuda.device(dev):

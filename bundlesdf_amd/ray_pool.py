@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import default_device
 
 POOL_MAX_PIXELS = 1 << 26        # frames per launch: F*H*W <= 64 M pixels (~3.2 GB of [P,12] f32 rows)
 
@@ -74,7 +75,7 @@ def make_pool_rays(frames, images, depths, masks, poses, K, cfg, occ_masks=None,
         return torch.empty((0, 12), dtype=torch.float32, device=device)
     if frames != list(range(frames[0], frames[0] + len(frames))):
         raise ValueError("make_pool_rays: frames must be consecutive ids")
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    device = default_device(device=device)
     L = _lib.lib()
     H, W = images.shape[1:3]
     sc = float(cfg["sc_factor"])

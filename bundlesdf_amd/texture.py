@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import default_device
 from .handoff import GLCAM_IN_CVCAM
 from .mesh import Mesh
 
@@ -58,7 +59,7 @@ def bake_texture(mesh, rgbs_raw, masks, cvcam_in_obs, K, H, W, min_depth, zfar, 
     values), masks [N,H,W(,1)], cvcam_in_obs [N,4,4] (OpenCV camera in object),
     K [3,3]. Returns the uint8 image [tex_res, tex_res, 3] (rows flipped, as the
     reference stores it)."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = default_device(device=device)
     L = _lib.lib()
     V = torch.as_tensor(np.asarray(mesh.vertices, np.float32), device=dev).contiguous()
     Fc = torch.as_tensor(np.asarray(mesh.faces, np.int64), device=dev).contiguous()
@@ -123,7 +124,7 @@ def vertex_colors_from_images(vertices, faces, images, masks, cvcam_in_obs, K, H
     [Nv,3] = clip(sum / count * 255, 0, 255) truncated, in float64 as the reference computes it;
     count int32 [Nv], the number of frames that coloured the vertex). A vertex with count 0 gets
     (0, 0, 0): the reference's 0/0 -> NaN -> uint8 cast is undefined."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = default_device(device=device)
     L = _lib.lib()
     V = torch.as_tensor(np.asarray(vertices, np.float32), device=dev).contiguous()
     Fc = torch.as_tensor(np.asarray(faces, np.int64), device=dev).contiguous()

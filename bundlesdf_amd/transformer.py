@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import PackedWeights, as_host, as_tensor, default_device
 
 __all__ = ["FeatureTransformer", "position_encoding", "add_position_encoding", "pack_matrix", "layer_bytes",
            "D_MODELS", "MAX_LAYERS", "MAX_PAIRS", "N_HEADS", "TILE"]
@@ -59,12 +60,12 @@ def position_encoding(h, w, C, temp_bug_fix=False, device=None):
 def add_position_encoding(feat, temp_bug_fix=False):
     """feat [P,C,h,w] (array or tensor, a backbone's coarse map) -> [P, h w, C] float32 on feat's device:
     the encoding added, then the reference's rearrange 'n c h w -> n (h w) c'."""
-    t = feat if torch.is_tensor(feat) else torch.from_numpy(np.array(feat))
+    t = as_tensor(feat)
     if t.dim() != 4 or not t.is_floating_point():
         raise ValueError(f"add_position_encoding: feat must be a floating-point [P,C,h,w], got {tuple(t.shape)} {t.dtype}")
     P, C, h, w = t.shape
     pe = position_encoding(h, w, C, temp_bug_fix, device=t.device)
-    return t.detach().float().permute(0, 2, 3, 1).reshape(P, h * w, C) + pe[None]
+    return t.float().permute(0, 2, 3, 1).reshape(P, h * w, C) + pe[None]
 
 
 def pack_matrix(W):
@@ -85,13 +86,7 @@ def _layer_keys(i, C):
             (p + "norm1.weight", (C,)), (p + "norm1.bias", (C,)), (p + "norm2.weight", (C,)), (p + "norm2.bias", (C,))]
 
 
-def _as_numpy(v):
-    if torch.is_tensor(v):
-        return v.detach().cpu().numpy()
-    return np.asarray(v)
-
-
-class FeatureTransformer:
+class FeatureTransformer(PackedWeights):
     """The stack of linear-attention layers with its weights packed for the device.
 
     weights maps the reference's parameter names (layers.{i}.{q_proj,k_proj,v_proj,merge}.weight,
@@ -114,22 +109,15 @@ class FeatureTransformer:
         parts = []
         for i in range(len(names)):
             for key, shape in _layer_keys(i, C):
-                if prefix + key not in weights:
-                    raise ValueError(f"{what}: key {prefix + key!r} is missing")
-                v = _as_numpy(weights[prefix + key])
-                if tuple(v.shape) != shape:
-                    raise ValueError(f"{what}: key {prefix + key!r} has shape {tuple(v.shape)}, expected {shape}")
+                v = self.lookup(weights, prefix, key, shape, what)
                 if len(shape) == 2:
                     parts.append(pack_matrix(v.astype(np.float16)).view(np.uint8).ravel())
                 else:
                     parts.append(np.ascontiguousarray(v.astype(np.float32)).view(np.uint8).ravel())
         self.d_model, self.layer_names = C, names
-        self.packed = np.concatenate(parts)
+        super().__init__(np.concatenate(parts), device)
         assert self.packed.size == len(names) * layer_bytes(C)
-        self._weights = {}          # device -> uint8 tensor
-        self._workspace = {}        # device -> uint8 tensor, grown on demand
-        if device is not None:
-            self._device_weights(torch.device(device))
+        self._workspace = self._buffers         # the name tests and scripts read
 
     @classmethod
     def from_state_dict(cls, sd, prefix=None, d_model=256, layer_names=("self", "cross") * 4, device=None):
@@ -137,34 +125,20 @@ class FeatureTransformer:
         'loftr_fine.', 'matcher.loftr_coarse.', ...); None finds it: the one prefix whose first query
         projection is [d_model, d_model]."""
         if prefix is None:
-            found = [k[:-len(_PROBE)] for k in sd if k.endswith(_PROBE)]
-            fit = [p for p in found if tuple(_as_numpy(sd[p + _PROBE]).shape) == (int(d_model), int(d_model))]
-            if len(fit) == 1:
-                prefix = fit[0]
-            elif len(found) == 1:
-                prefix = found[0]               # the shape check in __init__ names the key
-            elif not found:
-                raise ValueError(f"FeatureTransformer: key {_PROBE!r} is missing under every prefix")
-            else:
-                raise ValueError(f"FeatureTransformer: prefixes {sorted(found)} all hold a transformer, name one")
+            fit = [k[:-len(_PROBE)] for k in sd if k.endswith(_PROBE)
+                   and tuple(as_host(sd[k]).shape) == (int(d_model), int(d_model))]
+            # a lone prefix of another shape is taken too: the shape check in __init__ names the key
+            prefix = fit[0] if len(fit) == 1 else cls.find_prefix(sd, _PROBE, "FeatureTransformer", "a transformer")
         return cls(sd, d_model=d_model, layer_names=layer_names, device=device, prefix=prefix)
 
-    def _device_weights(self, dev):
-        dev = torch.device(dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._weights:
-            self._weights[dev] = torch.from_numpy(self.packed).to(dev)
-        return self._weights[dev]
-
     def _stream(self, f, name):
-        t = f if torch.is_tensor(f) else torch.from_numpy(np.array(f))
+        t = as_tensor(f)
         if not t.is_floating_point():
             raise ValueError(f"FeatureTransformer.forward: {name} must be a floating-point array, got {t.dtype}")
         if t.dim() not in (2, 3):
             raise ValueError(f"FeatureTransformer.forward: {name} must be [n,C] or [P,n,C], got {tuple(t.shape)}")
         single = t.dim() == 2
-        return (t.detach()[None] if single else t.detach()), single
+        return (t[None] if single else t), single
 
     def forward(self, feat_a, feat_b, mask_a=None, mask_b=None):
         """feat_a [P,L,C], feat_b [P,S,C] (arrays or tensors, float16 or float32; one [L,C] / [S,C] pair
@@ -185,38 +159,42 @@ class FeatureTransformer:
             raise ValueError(f"{what}: {P} pairs (1 .. {MAX_PAIRS})")
         if L < 1 or S < 1:
             raise ValueError(f"{what}: L={L} and S={S} must be at least 1")
-        dev = a.device if a.is_cuda else (b.device if b.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        dev = default_device(a if a.is_cuda else b)
         masks = []
         for m, n, name in ((mask_a, L, "mask_a"), (mask_b, S, "mask_b")):
             if m is None:
                 masks.append(None)
                 continue
-            t = m if torch.is_tensor(m) else torch.from_numpy(np.array(m))
-            t = t.detach()[None] if (single and t.dim() == 1) else t.detach()
+            t = as_tensor(m)
+            t = t[None] if (single and t.dim() == 1) else t
             if tuple(t.shape) != (P, n):
                 raise ValueError(f"{what}: {name} must be {[P, n]}, got {tuple(t.shape)}")
             masks.append((t != 0).to(torch.uint8).contiguous())
 
-        lib = _lib.lib()
         with torch.cuda.device(dev):
             # the kernels update the streams in place: these float32 copies are the outputs
             out_a = a.to(device=dev, dtype=torch.float32, copy=True).contiguous()
             out_b = b.to(device=dev, dtype=torch.float32, copy=True).contiguous()
             ma, mb = (None if m is None else m.to(dev) for m in masks)
-            w = self._device_weights(dev)
-            nbytes = int(lib.nof_feature_transformer_workspace_bytes(P, L, S, C))
-            ws = self._workspace.get(w.device)
-            if ws is None or ws.numel() < nbytes:
-                ws = self._workspace[w.device] = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
-            D = _lib.FeatureTransformerDesc()
-            D.feat_a, D.feat_b, D.mask_a, D.mask_b = (_lib.ptr(x) for x in (out_a, out_b, ma, mb))
-            D.P, D.L, D.S, D.C, D.n_layers = P, L, S, C, len(self.layer_names)
-            for i, n in enumerate(self.layer_names):
-                D.layer_kind[i] = _KINDS[n]
-            D.weights, D.weights_bytes = _lib.ptr(w), w.numel()
-            D.workspace, D.workspace_bytes = _lib.ptr(ws), ws.numel()
-            _lib.check(lib.nof_feature_transformer(ctypes.byref(D), _lib.stream_of(out_a)), what)
+            self._launch(out_a, out_b, ma, mb, what)
         return out_a, out_b
+
+    def _launch(self, a, b, mask_a, mask_b, what):
+        """nof_feature_transformer on a [P,L,C] and b [P,S,C], contiguous float32 on one device (the current
+        one), in place; mask_a / mask_b [P,L] / [P,S] u8 there, or None."""
+        P, L, C = a.shape
+        S = b.shape[1]
+        lib = _lib.lib()
+        w = self.device_weights(a.device)
+        ws = self.buffer(w.device, int(lib.nof_feature_transformer_workspace_bytes(P, L, S, C)))
+        D = _lib.FeatureTransformerDesc()
+        D.feat_a, D.feat_b, D.mask_a, D.mask_b = (_lib.ptr(x) for x in (a, b, mask_a, mask_b))
+        D.P, D.L, D.S, D.C, D.n_layers = P, L, S, C, len(self.layer_names)
+        for i, n in enumerate(self.layer_names):
+            D.layer_kind[i] = _KINDS[n]
+        D.weights, D.weights_bytes = _lib.ptr(w), w.numel()
+        D.workspace, D.workspace_bytes = _lib.ptr(ws), ws.numel()
+        _lib.check(lib.nof_feature_transformer(ctypes.byref(D), _lib.stream_of(a)), what)
 
     def forward_inplace(self, a, b):
         """The stack on a [P,L,C] and b [P,S,C], contiguous float32 tensors on one device, updated where
@@ -237,21 +215,8 @@ class FeatureTransformer:
             raise ValueError(f"{what}: L={L} and S={S} must be at least 1")
         if not a.is_cuda or a.device != b.device:
             raise ValueError(f"{what}: a is on {a.device} and b on {b.device}: one device is needed")
-        lib = _lib.lib()
         with torch.cuda.device(a.device):
-            w = self._device_weights(a.device)
-            nbytes = int(lib.nof_feature_transformer_workspace_bytes(P, L, S, C))
-            ws = self._workspace.get(w.device)
-            if ws is None or ws.numel() < nbytes:
-                ws = self._workspace[w.device] = torch.empty(max(1, nbytes), dtype=torch.uint8, device=a.device)
-            D = _lib.FeatureTransformerDesc()
-            D.feat_a, D.feat_b = _lib.ptr(a), _lib.ptr(b)
-            D.P, D.L, D.S, D.C, D.n_layers = P, L, S, C, len(self.layer_names)
-            for i, n in enumerate(self.layer_names):
-                D.layer_kind[i] = _KINDS[n]
-            D.weights, D.weights_bytes = _lib.ptr(w), w.numel()
-            D.workspace, D.workspace_bytes = _lib.ptr(ws), ws.numel()
-            _lib.check(lib.nof_feature_transformer(ctypes.byref(D), _lib.stream_of(a)), what)
+            self._launch(a, b, None, None, what)
         return a, b
 
     __call__ = forward
