@@ -18,7 +18,7 @@ def golden(golden_dir):
     return O.load_golden(golden_dir)
 
 
-@pytest.mark.parametrize("case", list(O.CASES))
+@pytest.mark.parametrize("case", O.STORED)
 def test_oracle_reproduces_the_reference_module(golden, case):
     """Two float64 evaluations of one formula: the error is O(1e-13), the bound 1e-9 absolute."""
     w, a, b, ma, mb = O.case_data(case)
@@ -39,6 +39,59 @@ def test_fixture_sees_the_cross_order(golden):
     oa, ob = O.forward(w, O.CASES["cross1"]["layers"], a, b, cross_b_first=True)
     err = max(np.abs(oa - golden["cross1_a64"]).max(), np.abs(ob - golden["cross1_b64"]).max())
     assert err > 100 * float(golden["cross1_e16_max"])
+
+
+@pytest.mark.parametrize("case", list(O.CASES))
+def test_fixture_holds_a_half_precision_error_for_every_case(golden, case):
+    """e16 is what every GPU bound is a multiple of. It is a handful of fp16 roundings (each up to 2^-11
+    relative) of values of the outputs' size: between 2^-13 and 2^-9 of the oracle's output rms, and its
+    largest element within 16 rms. For the cases without stored outputs this ties the recorded scalars to
+    the oracle's outputs of the same case."""
+    e_rms, e_max = float(golden[f"{case}_e16_rms"]), float(golden[f"{case}_e16_max"])
+    out = O.flat(O.case_output(case))
+    rms = float(np.sqrt(np.mean(out ** 2)))
+    assert np.isfinite(out).all() and 2.0 ** -13 * rms <= e_rms <= 2.0 ** -9 * rms, (case, e_rms, rms)
+    assert e_rms <= e_max <= 16 * e_rms, (case, e_rms, e_max)
+
+
+@pytest.mark.parametrize("mutant", list(O.MUTANTS))
+def test_named_cases_tell_a_mutant_from_the_definition(golden, mutant):
+    """rms(d_m) >= factor x e16_rms on every case the table names for the mutant: 6 for the structural ones
+    (2 x e16 for the kernels plus the same again, with room), 1 for a wrong constant or divisor."""
+    cases, factor = O.MUTANTS[mutant]
+    for case in cases:
+        d = O.mutant_delta(case, mutant)
+        dist = float(np.sqrt(np.mean(d ** 2))) / float(golden[f"{case}_e16_rms"])
+        print(f"{mutant} {case}: {dist:.1f} e16_rms")
+        assert dist >= factor, (mutant, case, dist)
+
+
+def test_eps_shows_only_in_the_amplifying_cases(golden):
+    """At the ordinary weights a LayerNorm eps of 1e-6 is below e16: no bound on the output can see it. With
+    merge.weight and mlp.2.weight scaled down, the variance both LayerNorms see is of the order of eps and the
+    same mutant is hundreds of e16 away."""
+    for mutant in ("ln1_eps", "ln2_eps"):
+        d = O.mutant_delta("self1", mutant)
+        assert np.sqrt(np.mean(d ** 2)) < float(golden["self1_e16_rms"])
+        for case in ("amp256", "amp128"):
+            d = O.mutant_delta(case, mutant)
+            assert np.sqrt(np.mean(d ** 2)) > 100 * float(golden[f"{case}_e16_rms"])
+
+
+def test_a_masked_query_is_x_plus_the_feed_forward_of_bias1():
+    """The oracle's rows with mask 0: msg is exactly 0, LayerNorm1 of zeros is its bias, so the row is
+    x + LN2(relu([x | bias1] W1^T) W2^T) and no source enters it."""
+    case = "edge_64_65"
+    w, a, b, ma, mb = O.case_data(case)
+    g = lambda name: w["layers.0." + name].astype(np.float64)
+    out_a = O.case_output(case, True)[0]
+    assert (~ma).sum() > 0
+    x = a.astype(np.float64)[~ma]
+    hid = np.maximum(np.concatenate([x, np.broadcast_to(g("norm1.bias"), x.shape)], 1) @ g("mlp.0.weight").T, 0.0)
+    y = hid @ g("mlp.2.weight").T
+    mu = y.mean(-1, keepdims=True)
+    ln2 = (y - mu) / np.sqrt(((y - mu) ** 2).mean(-1, keepdims=True) + 1e-5) * g("norm2.weight") + g("norm2.bias")
+    assert np.abs(out_a[~ma] - (x + ln2)).max() <= 1e-12
 
 
 @pytest.mark.parametrize("fix", [False, True])
